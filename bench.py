@@ -15,10 +15,16 @@ itself: it starts `torch.distributed.run` as a CHILD process before anything her
 rank 0's line.
 
 Prints ONE JSON line (rank 0).  `value` times K pipelined steps (loss read back once, after the region, as
-`train_net` does between display iterations); the JSON also carries the fully synchronous `train_step` rate
-(the reference reads its losses back every step, NET:704-710), the rate with the 7.2 MB image re-uploaded
-every step, the roofline of the dominant launch, of the whole 3x3 stack and of the time-dominant group of
-convolution launches, and the CPU restatement timed on this box's host cores."""
+`train_net` does between display iterations).  A plain run does only that: set up, warm up, time the K steps, print.
+With `--full` the JSON also carries the fully synchronous `train_step` rate (the reference reads its losses back
+every step, NET:704-710), the rate with the 7.2 MB image re-uploaded every step, the mixed-shape and exact-f32
+rates, the roofline of the dominant launch, of the whole 3x3 stack and of the time-dominant group of convolution
+launches, and the CPU restatement timed on this box's host cores.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (float32): the device
+loss buffer, and the updated weights and momentum at a fixed, seeded sample of positions of the flat parameter
+buffer (see `timed_outputs`).  The inputs and initial weights are seeded, so two builds can be compared output
+for output."""
 import argparse
 import json
 import re
@@ -79,17 +85,24 @@ def parse_args(argv=None):
     ap.add_argument('--dtype', default='bf16')
     ap.add_argument('--variant', default='cycle', choices=VARIANT_CHOICES,
                     help='network variant = BASELINE.json config: cycle (the headline, config 3), baseline (1), spatial (2), cycle_response (4), vgg (5)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-baseline-steps', default='3,10', help='W,K: warm-up and timed steps of the CPU restatement (BASELINE.md section 3: 3 + 10, ~2-3 min on the GPU box)')
+    ap.add_argument('--cpu-baseline-steps', '--no-cpu-baseline', nargs='?', const='0,0', default='3,10',
+                    help='with --full, W,K: warm-up and timed steps of the CPU restatement (BASELINE.md section 3: 3 + 10, ~2-3 min on an MI355X host); '
+                         '--no-cpu-baseline = 0,0: no CPU leg')
     ap.add_argument('--dp-wire', default='', choices=['', 'fp32', 'bf16'], help='gradient buckets on the wire: fp32 (282 MB / step) or packed to bf16 (141 MB); default: bf16 for N > 1')
     ap.add_argument('--dp-algo', default='', choices=['', 'allreduce', 'rs_ag'], help='one all-reduce per bucket, or reduce-scatter + all-gather; default: rs_ag for N > 1')
     ap.add_argument('--dp-shard-update', type=int, default=-1, help='with rs_ag: every rank updates only its slice of a bucket and the WEIGHTS are all-gathered; default: on for N > 1')
-    ap.add_argument('--mixed-shapes', type=int, default=1, help='extra leg: a stream of six different (image size, token count) shapes replayed from pre-recorded tapes')
+    ap.add_argument('--mixed-shapes', type=int, default=1, help='with --full: a stream of six different (image size, token count) shapes replayed from pre-recorded tapes')
     ap.add_argument('--height', type=int, default=600)
     ap.add_argument('--width', type=int, default=1000)
-    ap.add_argument('--extras', type=int, default=1, help='0: only the headline timing (no synchronous / PCIe-inclusive / per-launch legs)')
+    ap.add_argument('--full', '--extras', type=int, nargs='?', const=1, default=0,
+                    help='every side leg besides the headline: synchronous / PCIe-inclusive / drop-in / mixed-shape / exact-f32 rates, per-launch roofline, '
+                         'CPU baseline (a plain run times the headline alone; --extras N is the older spelling, 0 = plain)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (float32)')
     ap.add_argument('--launcher-check', action='store_true', help='only bring the ranks up (gloo without GPUs), count them with an all-reduce, print the line')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def spawn_ranks(args, argv):
@@ -152,6 +165,24 @@ def cpu_baseline(H, W, T, V, warm, timed, variant='cycle'):
             's_per_step': dt, 's_per_step_all': [round(t, 3) for t in ts],
             'sample': '%d warm-up + %d timed train steps of the %s variant (%dx%d image, %d tokens, 256 RoIs, fp32, torch-CPU restatement in oracle/), mean %.1f s / step'
                       % (warm, timed, variant, H, W, T, dt)}
+
+
+DUMP_SAMPLE = 4 << 20        # positions of the flat parameter buffer in the dump (the buffer holds ~70 M floats): 2 x 16 MB
+
+
+def timed_outputs(net, loss):
+    """What a caller of the timed path holds after its last step, as float32 host arrays: the device loss buffer the step returned, and the
+    network's updated fp32 weights and SGD momentum (the momentum carries the step's gradients; the update kernel zeroes the gradient buffer
+    it consumes) at a fixed, seeded sample of positions of the flat parameter buffer - the same positions on every run and build."""
+    import numpy as np
+    import torch
+    P = net.P
+    n = int(P.param.numel())
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.unique(np.random.RandomState(20251015).randint(0, n, size=DUMP_SAMPLE))
+    it = torch.from_numpy(idx.astype(np.int64)).to(P.param.device)
+    return {'losses': loss.detach().float().cpu().numpy(),
+            'weights_sample': P.param.index_select(0, it).float().cpu().numpy(),
+            'momentum_sample': P.mom.index_select(0, it).float().cpu().numpy()}
 
 
 def _baseline_metric():
@@ -520,7 +551,7 @@ def main(argv=None, hooks=None):
             return float(tt.item())
         return dt
 
-    lt = LaunchTimer(net, torch)
+    lt = LaunchTimer(net, torch) if args.full else None       # timing events on the tape and per-launch plan tracking: side legs only
     for i in range(args.warmup):
         net.train_step_async(blobs[i % 4], 0, optim)
     barrier()
@@ -531,10 +562,11 @@ def main(argv=None, hooks=None):
     barrier()
     dt = rank_max(time.time() - t0)
     lv = loss.cpu().numpy()
+    dumped = timed_outputs(net, loss) if args.dump_outputs and rank == 0 else None     # before any side leg moves the weights on
     # ---- the dominant launch inside the pipelined replay: HIP events on its stream, recorded by the tape in every step; the events now hold
     # the LAST step of the timed region; four more pipelined pairs of steps give further samples (outside the timed region) ----
     dom_ms = []
-    if lt.tape_pairs:
+    if lt is not None and lt.tape_pairs:
         dom_ms += [lt.O.time_event_elapsed(a, b) for a, b in lt.tape_pairs]
         for rep in range(4):
             for i in range(2):
@@ -543,7 +575,7 @@ def main(argv=None, hooks=None):
             dom_ms += [lt.O.time_event_elapsed(a, b) for a, b in lt.tape_pairs]
     # ---- per-launch times of EVERY convolution / grouped weight-gradient launch inside pipelined replayed steps: a second tape with a timing
     # event before and after each of those launches (outside the timed region: ~400 event records per step) ----
-    if args.extras and getattr(net, 'use_tape', False) and world == 1:
+    if args.full and getattr(net, 'use_tape', False) and world == 1:
         lt.tape_all = True
         while getattr(net, '_tapes', None):
             net._evict_tape()
@@ -571,7 +603,7 @@ def main(argv=None, hooks=None):
             rep = net.dp.report()                   # HIP events of the LAST timed step: per-bucket exchange time, and what the main stream waited for
             if rep is not None:
                 extras['dp'] = rep
-    if args.extras:
+    if args.full:
         # ---- the reference's unit as it stands: train_step() reads the losses back every step (NET:704-710: seven .data[0]) ----
         # (the measurement leg above evicted every launch tape: two untimed steps record the step's tape again - until round 6 that recording,
         # an eagerly issued step with two device syncs, sat inside this leg's timed region and cost it ~4 %: sync came out BELOW dropin)
@@ -654,7 +686,7 @@ def main(argv=None, hooks=None):
         lt.on = False
     # ---- the exact-f32 verification mode beside the bf16 headline: the mode in which losses / seg-logits match the reference
     # to 1e-4 and the proposal lists to the box (tests/test_train_step_gpu.py f32 legs); its own network, same inputs, pipelined like the headline
-    if args.extras and world == 1 and args.dtype == 'bf16' and not experiment:
+    if args.full and world == 1 and args.dtype == 'bf16' and not experiment:
         try:
             cfg.COMPUTE_DTYPE = 'f32'
             if variant == 'vgg':
@@ -714,7 +746,7 @@ def main(argv=None, hooks=None):
             out['experiment'] = 'INVALID as a measurement: collectives staged through the host on a %s group (functional run of the N > 1 path)' % hooks.dp_backend
         if experiment:
             out['experiment'] = 'INVALID as a measurement: knockout=%s dp_skip_allreduce=%d' % (sorted(net.knockout), hooks.dp_skip_allreduce)
-        if args.extras:
+        if args.full:
             tab, stack, dom = lt.summary(NE)
             dk = [r for r in lt.recs if r[0] == 'layer4@RoIs' and r[1] == 'fwd' and r[2] == 3]
             kflop = 2.0 * (R * 49) * 512 * 4608
@@ -769,9 +801,14 @@ def main(argv=None, hooks=None):
                 out['roofline'] = dict(best, bound='mfma', best=best, stack3x3=stack, groups=tab)
         else:
             out['roofline'] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full:
             w, k = [int(x) for x in args.cpu_baseline_steps.split(',')]
-            out['cpu_baseline'] = cpu_baseline(args.height, args.width, T, V, w, k, variant)
+            if k > 0:
+                out['cpu_baseline'] = cpu_baseline(args.height, args.width, T, V, w, k, variant)
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + '.npy'), a)
         emit(out)
     if use_dp:
         dist.destroy_process_group()

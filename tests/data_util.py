@@ -19,6 +19,26 @@ def load_rle_fixture():
     return cases, groups
 
 
+def live_rle_masks():
+    """the 40 random masks the reference library is checked on live (test_oracle_rle_matches_reference_library_live)"""
+    rs = np.random.RandomState(1)
+    for _ in range(40):
+        h, w = int(rs.randint(1, 90)), int(rs.randint(1, 90))
+        yield (rs.rand(h, w) < rs.uniform(0.02, 0.98)).astype(np.uint8)
+
+
+def load_rle_live_fixture():
+    """what the reference library returned for live_rle_masks(): [(string, counts, decoded mask)] (tests/golden/ref_rle_live.npz)"""
+    g = dict(np.load(os.path.join(GOLD, 'ref_rle_live.npz'), allow_pickle=False))
+    out = []
+    for i in range(len(g['h'])):
+        h, w = int(g['h'][i]), int(g['w'][i])
+        cnt = g['counts'][g['counts_off'][i]:g['counts_off'][i + 1]]
+        bits = np.unpackbits(g['masks_packed'][g['masks_off'][i]:g['masks_off'][i + 1]])[:h * w].reshape(h, w)
+        out.append((g['strings'][i].decode('ascii'), cnt, bits.astype(np.uint8)))
+    return out
+
+
 def write_tiny_dataset(root, seed=0, sizes=((120, 160), (90, 150), (200, 140)), label_length=8, vocab=30):
     """data.json + data.h5.npy + PNG images (lossless, so the decoded pixels are the written ones) under `root`.
     Layout of lib/loaders/cycle_loader.py's docstring; refs hold 'rle' lists as the reference's prepro writes them."""

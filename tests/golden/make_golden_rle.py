@@ -4,7 +4,9 @@
 
 Every case: a binary mask (or a polygon) -> rleEncode / rleFrPoly -> rleToString  (the `counts` strings data.json holds) ->
 rleFrString -> rleDecode.  Stored: size, string, the run lengths the reference parsed, the decoded mask (bit-packed).
-Run here (needs /root/reference for the build):  make -C oracle && python tests/golden/make_golden_rle.py"""
+Also tests/golden/ref_rle_live.npz: the same library's string, run lengths and decoded mask for the 40 random masks of
+test_oracle_rle_matches_reference_library_live (tests/data_util.live_rle_masks), which it checks against where the library is not built.
+Run where the reference sources lie under REF (oracle/Makefile):  make -C oracle && python tests/golden/make_golden_rle.py"""
 import os
 import sys
 
@@ -63,6 +65,23 @@ def main():
     np.savez_compressed(out, h=H, w=W, strings=strings, counts=np.concatenate(cnt_list).astype(np.uint32), counts_off=offs,
                         masks_packed=packed, masks_off=moffs, groups=np.array([g + [-1] * (3 - len(g)) for g in groups], np.int32))
     print('wrote', out, len(cases), 'cases', os.path.getsize(out), 'bytes')
+    write_live(api)
+
+
+def write_live(api):
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    from data_util import live_rle_masks
+    masks = list(live_rle_masks())
+    strings = [api.encode(m) for m in masks]
+    cnt_list = [api.counts(s, m.shape[0], m.shape[1]) for s, m in zip(strings, masks)]
+    dec = [api.decode(s, m.shape[0], m.shape[1]) for s, m in zip(strings, masks)]
+    out = os.path.join(ROOT, 'tests', 'golden', 'ref_rle_live.npz')
+    np.savez_compressed(out, h=np.array([m.shape[0] for m in masks], np.int32), w=np.array([m.shape[1] for m in masks], np.int32),
+                        strings=np.array([s.encode('ascii') for s in strings]), counts=np.concatenate(cnt_list).astype(np.uint32),
+                        counts_off=np.concatenate([[0], np.cumsum([len(c) for c in cnt_list])]).astype(np.int64),
+                        masks_packed=np.concatenate([np.packbits(d.reshape(-1)) for d in dec]),
+                        masks_off=np.concatenate([[0], np.cumsum([(d.size + 7) // 8 for d in dec])]).astype(np.int64))
+    print('wrote', out, len(masks), 'cases', os.path.getsize(out), 'bytes')
 
 
 if __name__ == '__main__':

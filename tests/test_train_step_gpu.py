@@ -1492,11 +1492,11 @@ def test_random_init_network_stays_finite(variant):
 
 
 def test_bench_json_contract():
-    """bench.py prints exactly one JSON line on stdout with the driver's keys (BASELINE.json's metric string verbatim, the roofline
+    """bench.py --full prints exactly one JSON line on stdout with the driver's keys (BASELINE.json's metric string verbatim, the roofline
     and cpu_baseline objects); run at the full BASELINE shape with a handful of steps."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--cpu-baseline-steps', '1,1'], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '3', '--warmup', '1', '--cpu-baseline-steps', '1,1'], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -1536,3 +1536,30 @@ def test_bench_workload_learns_when_pipelined():
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
     rpn_cls, _, cls = d['final_losses'][:3]
     assert cls < 4.3 and rpn_cls < 0.69, d['final_losses']
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """a plain bench.py run (no --full) times the headline alone - none of the side legs' keys on its line - and --dump-outputs writes the
+    last timed step's loss buffer and the seeded weight / momentum samples as float32 .npy files, 64 MB at most, agreeing with the line."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / 'outputs')
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '2', '--warmup', '1', '--dump-outputs', out],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d['metric'] == json.load(open(os.path.join(root, 'BASELINE.json')))['metric'] and d['unit'] == 'img/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'bf16' and d['steps'] == 2 and d['warmup'] == 1 and abs(d['value'] - 1000.0 / d['ms_per_step']) < 1e-6 * d['value']
+    for k in ('cpu_baseline', 'sync_train_step', 'pcie_inclusive', 'dropin_train_step', 'mixed_shapes', 'f32_train_step'):
+        assert k not in d, k
+    assert d['roofline'] is None
+    names = sorted(os.listdir(out))
+    assert names == ['losses.npy', 'momentum_sample.npy', 'weights_sample.npy'], names
+    arrs = {n[:-4]: np.load(os.path.join(out, n)) for n in names}
+    assert all(a.dtype == np.float32 for a in arrs.values())
+    assert sum(os.path.getsize(os.path.join(out, n)) for n in names) <= 64 << 20
+    assert np.array_equal(arrs['losses'][:7], np.asarray(d['final_losses'], dtype=np.float32))
+    w, m = arrs['weights_sample'], arrs['momentum_sample']
+    assert w.shape == m.shape and w.size > 1 << 20 and np.isfinite(w).all() and np.isfinite(m).all() and np.abs(m).max() > 0

@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r5; mkdir -p $O; cd $R
 : > $O/bench_variants.json
 for v in cycle spatial cycle_response vgg baseline; do
-  timeout 600 python bench.py --variant $v --no-cpu-baseline --mixed-shapes 0 --steps 50 --warmup 10 2>$O/variant_$v.err | grep '^{' | tail -1 >> $O/bench_variants.json || echo "FAILED $v"
+  timeout 600 python bench.py --full --variant $v --no-cpu-baseline --mixed-shapes 0 --steps 50 --warmup 10 2>$O/variant_$v.err | grep '^{' | tail -1 >> $O/bench_variants.json || echo "FAILED $v"
   tail -3 $O/variant_$v.err | cut -c1-300
 done
 python - <<'PY'

@@ -18,7 +18,7 @@ timeout 300 python tools/step_timeline.py > $O/step_timeline.txt 2>&1
 timeout 200 python tools/build_tools_lib.py > /dev/null 2>&1
 { timeout 200 python tools/nms_cycles.py tests/golden/nms_deep_boxes.npy; } > $O/nms_cycles.txt 2>&1
 { timeout 200 python tools/backbone_alone.py; timeout 200 python tools/cold_weights_bench.py; timeout 200 python tools/host_time.py; timeout 300 python tools/clock_probe.py; } > $O/step_diagnostics.txt 2>&1
-timeout 900 python bench.py > $O/bench_final.log 2>&1; grep '^{' $O/bench_final.log | tail -1 > $O/bench_final.json
+timeout 900 python bench.py --full > $O/bench_final.log 2>&1; grep '^{' $O/bench_final.log | tail -1 > $O/bench_final.json
 timeout 2400 bash tools/r5_variants.sh > $O/variants.log 2>&1; cp gpurun_out/r5/bench_variants.json $O/bench_variants.json
 timeout 2400 bash tools/r6_dp_matrix.sh > /dev/null 2>&1; cp gpurun_out/r6/dp_onerank_matrix.txt $O/
 hipcc --offload-arch=gfx950 -O3 -Wno-unused-result tools/cap_allgather_probe.hip -o /tmp/cap_ag_probe 2>/dev/null && timeout 120 /tmp/cap_ag_probe > $O/cap_allgather_probe.txt 2>&1

@@ -11,9 +11,9 @@ Round 4 added a second pattern: packed fp32 VALU ops (v_pk_fma_f32, v_pk_add_f32
 gave sporadically wrong low halves beside other queues' kernels (tools/vgg_corun_fuzz.py); the library is built with the target feature
 `packed-fp32-ops` off (__graft_entry__.HIPCC_FLAGS) and this scan checks that none is left in any kernel.
 
-    python tools/scan_lgkm_order.py            # compiles lang2seg_amd/csrc/*.hip to assembly under /tmp and scans them
+    python tools/scan_lgkm_order.py            # compiles lang2seg_amd/csrc/*.hip to assembly in a private temporary directory and scans them
 """
-import glob, os, re, subprocess, sys
+import glob, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -55,8 +55,9 @@ def scan(path):
 def main():
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     bad = 0
+    tmp = tempfile.TemporaryDirectory(prefix='l2s_scan_')          # per run: a fixed shared path fails where another user's files lie
     for src in sorted(glob.glob(os.path.join(ROOT, 'lang2seg_amd', 'csrc', '*.hip'))):
-        asm = os.path.join('/tmp', 'l2s_scan_' + os.path.basename(src)[:-4] + '.s')
+        asm = os.path.join(tmp.name, os.path.basename(src)[:-4] + '.s')
         sys.path.insert(0, ROOT)
         from __graft_entry__ import HIPCC_FLAGS                      # the flags the library is built with
         subprocess.run([hipcc] + [f for f in HIPCC_FLAGS if f != '-fPIC'] + ['-I' + os.path.join(ROOT, 'include'), '-S', '--cuda-device-only',
@@ -64,6 +65,7 @@ def main():
         for fn, n in scan(asm).items():
             print('%s: %d site(s) in %s' % (os.path.basename(src), n, fn))
             bad += n
+    tmp.cleanup()
     print('sites: %d' % bad)
     return 1 if bad else 0
 
