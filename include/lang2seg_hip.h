@@ -478,6 +478,22 @@ long l2s_rle_ws_words(int total_counts, int oh, int ow);
 int l2s_rle_to_mask(const uint32_t* cnts, const int* offs, int n, int total_counts, int h, int w, int oh, int ow,
                     uint32_t* ws, uint8_t* out, hipStream_t s);
 
+/* ---------------------------------------------------------------- evaluation (model/eval_device.py) ----- */
+/* One sentence's result, in a caller-owned device array (48 bytes): the picked (roi, class), its box in the original image,
+ * box hit (IoU >= 0.5), and the mask's intersection / union pixel counts. */
+typedef struct { int roi; int cls; float box[4]; int hit; int reserved; long long I; long long U; } l2s_eval_record;
+/* Device, one workgroup.  model/test.py best_detection over cls_prob [post][ncls] rows < *nkeep (nkeep NULL: all `post` rows; rows
+ * behind it are padding and ignored) + detect_from_outputs / bbox_transform_inv_np / _clip_boxes on the chosen row (im_h, im_w: the
+ * original image size round(im_info / scale); bbox_reg = cfg.TEST.BBOX_REG) + computeIoU_box against gt_box (x1 y1 x2 y2, scaled
+ * image) / im_scale.  Writes *rec with I = U = 0, the mask head's RoI [5] (batch index 0, pred_box * im_scale) and its class label. */
+int l2s_eval_pick(const float* cls_prob, const float* bbox_pred, const float* rois, const int* nkeep, int post, int ncls, float im_scale,
+                  int im_h, int im_w, const float* gt_box, int bbox_reg, l2s_eval_record* rec, float* mask_roi, int* mask_label, hipStream_t s);
+/* Device.  segment_from_mask_prob of the chosen class's [ms][ms] probabilities (ms <= 16) on rec->box into an ih x iw canvas (bytescale,
+ * Pillow 8-bit BILINEAR, paste, > 122) against the gt mask [Hs][Ws] uint8 PIL-NEAREST resized to ih x iw: adds the intersection and
+ * union pixel counts to rec->I, rec->U (integer atomics).  canvas: optional uint8 [ih][iw] dump of the predicted mask (checks). */
+int l2s_eval_mask_iou(const float* mask_prob, int ms, l2s_eval_record* rec, const uint8_t* gt, int Hs, int Ws, int ih, int iw,
+                      uint8_t* canvas, hipStream_t s);
+
 /* ---------------------------------------------------------------- launch tape / streams ----- */
 /* `to` waits (device side) for everything enqueued so far on `from`; fork or join of the step's branches */
 int l2s_stream_fork(hipStream_t from, hipStream_t to);

@@ -7,6 +7,7 @@
 //   l2s_rle_to_mask       device   maskApi.c:43-47 (rleDecode) + cycle_loader.py:205-209 (sum over segments > 0, imresize nearest)
 #include "common.h"
 #include "../../include/lang2seg_hip.h"
+#include "pil_resize.h"
 #include <cmath>
 
 namespace {
@@ -36,21 +37,11 @@ __global__ __launch_bounds__(1024) void rle_scan_kernel(const uint32_t* cnts, co
     __syncthreads();
   }
 }
-// PIL NEAREST source index of every output row / column (oracle/boxes.py nearest_index: xo = 0.5 s, then += s in float64)
+// PIL NEAREST source index of every output row / column (pil_resize.h)
 __global__ void nearest_table_kernel(int h, int oh, int w, int ow, int* ty, int* tx) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < oh) {
-    const double s = (double)h / (double)oh;
-    double xo = 0.5 * s;
-    for (int i = 0; i < k; ++i) xo += s;
-    ty[k] = min((int)xo, h - 1);
-  }
-  if (k < ow) {
-    const double s = (double)w / (double)ow;
-    double xo = 0.5 * s;
-    for (int i = 0; i < k; ++i) xo += s;
-    tx[k] = min((int)xo, w - 1);
-  }
+  if (k < oh) ty[k] = pil_nearest_src(k, h, oh);
+  if (k < ow) tx[k] = pil_nearest_src(k, w, ow);
 }
 // out[y][x] = 1 if any object covers source pixel (ty[y], tx[x]); an object's runs are over the column-major index x*h + y and
 // alternate 0,1,0,... (maskApi.c:43-47), so the pixel's value is the parity of the run that holds its index (binary search)

@@ -178,12 +178,13 @@ class CycleLoader(Loader):
         return data
 
     # ---- getTestBatch (gt_mrcn_loader.py:633-741; the cycle eval scripts use the same method)
-    def getTestBatch(self, split):
+    def getTestBatch(self, split, stride=1):
+        """stride > 1: the cursor advances by that many images (rank-sharded evaluation, model/eval_device.py starts it at the rank)"""
         split_ix = self.split_ix[split]
         max_index = len(split_ix) - 1
         wrapped = False
         ri = self.iterators[split]
-        ri_next = ri + 1
+        ri_next = ri + stride
         if ri_next > max_index:
             ri_next = 0
             wrapped = True

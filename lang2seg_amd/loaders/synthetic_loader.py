@@ -50,11 +50,19 @@ class SyntheticLoader(object):
 
     def getBatch(self, split, batch_size=1):
         assert batch_size == 1
+        return self._next(split, 1)
+
+    def getTestBatch(self, split, stride=1):
+        """getBatch for evaluation; `stride` > 1 advances the cursor by that many images (rank-sharded evaluation, model/eval_device.py:
+        the caller starts the cursor at its rank) and wraps once it passes the end"""
+        return self._next(split, stride)
+
+    def _next(self, split, stride):
         si = self.iterators[split]
         n = len(self.split_ix[split])
         wrapped = False
         ix = self.split_ix[split][self.perm[split][si]]
-        si += 1
+        si += stride
         if si >= n:
             si = 0
             wrapped = True
@@ -68,5 +76,3 @@ class SyntheticLoader(object):
         else:
             self._cache[('dev', ix)] = blob          # device copies made by Network.upload_blob stay with the image
         return self._cache[('dev', ix)]
-
-    getTestBatch = getBatch

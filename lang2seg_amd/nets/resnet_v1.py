@@ -980,12 +980,10 @@ class resnetv1(Network):
 
 
     # ------------------------------------------------------------------ TEST mode (NET:488-593 mode == 'TEST', 595-626, 650-658)
-    def _backbone_and_filter(self, d):
-        """conv1..layer3, expression encoding, dynamic filters -> (net_conv, base, Hc, Wc); single stream (inference)."""
+    def _test_filter(self, d):
+        """expression encoding + the dynamic filters' linear layer (TEST mode) -> filt [7 * C4 + 7]"""
         P = self.P
         C4 = self._C4_feat_dim
-        H, W = int(d['data'].shape[1]), int(d['data'].shape[2])
-        self.join_update()
         hidden = self._encoder_fwd(d)
         HD = hidden.numel()
         NF, NFP = 7 * C4 + 7, self._NFP
@@ -995,9 +993,20 @@ class resnetv1(Network):
             if not hasattr(self, '_r_one'):
                 self._r_one = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], dtype=f32, device=self.device)
             O.memcpy(filt[7 * C4:], self._r_one)
-        base, Hc, Wc = self._backbone_fwd(d, {})
+        return filt
+
+    def _test_dynfilter(self, filt, base, Hc, Wc):
+        C4 = self._C4_feat_dim
         net_conv = self.buf('dyn.y', (Hc * Wc, C4)); resp = self.buf('dyn.resp', (Hc * Wc,), f32); respk = self.buf('dyn.respk', (Hc * Wc, 7), f32)
         O.dynfilter_fwd(base, filt, filt[7 * C4:], net_conv, resp, respk, Hc, Wc, C4, gate=1 if self.var['gate'] == 'sigmoid' else 0)
+        return net_conv, resp
+
+    def _backbone_and_filter(self, d):
+        """conv1..layer3, expression encoding, dynamic filters -> (net_conv, base, Hc, Wc); single stream (inference)."""
+        self.join_update()
+        filt = self._test_filter(d)
+        base, Hc, Wc = self._backbone_fwd(d, {})
+        net_conv, resp = self._test_dynfilter(filt, base, Hc, Wc)
         return net_conv, base, resp, Hc, Wc
 
     def _roi_heads_test(self, net_conv, Hc, Wc, rois, n, labels=None):
@@ -1030,14 +1039,27 @@ class resnetv1(Network):
             O.mask_prob(mscore, nc, nc, labels, MS * MS, n * MS * MS, mprob)
         return cheads, cls_prob, bbox_pred, mprob
 
-    def forward_test(self, d):
-        """NET:628-662 with mode == 'TEST'.  Fills self._predictions like the reference (device tensors, NHWC / row-major)."""
+    def forward_test_image(self, d):
+        """the image half of the TEST forward: conv1..layer3 once per image (the backbone depends on the image only).  Its output buffer
+        survives any number of forward_test_sentence calls: the sentence half writes other buffers."""
         self.join_transposes()
         self.t = {}
+        self.join_update()
+        base, Hc, Wc = self._backbone_fwd(d, {})
+        self._test_base = (base, Hc, Wc)
+        return base, Hc, Wc
+
+    def forward_test_sentence(self, d):
+        """the sentence half of the TEST forward on the backbone map of the last forward_test_image: expression encoding, dynamic filters,
+        RPN, proposals and the heads on all `post` slots.  No host synchronisation (except TEST.MODE 'top' with fewer anchors than
+        RPN_TOP_N, whose draw is numpy's): device buffers + the device keep count `nkeep` (None: all `post` rows are real)."""
         A = self._num_anchors
         im_h, im_w = float(d['im_info'][0]), float(d['im_info'][1])
         self._im_hw = (im_h, im_w)
-        net_conv, base, resp, Hc, Wc = self._backbone_and_filter(d)
+        self.join_update()
+        filt = self._test_filter(d)
+        base, Hc, Wc = self._test_base
+        net_conv, resp = self._test_dynfilter(filt, base, Hc, Wc)
         HW = Hc * Wc
         P = self.P
         rpn = self.buf('rpn.a', (HW, 512))
@@ -1060,7 +1082,6 @@ class resnetv1(Network):
                 # fewer anchors than RPN_TOP_N (:44-49): drawn with replacement from numpy's generator, as the reference does
                 idx = torch.from_numpy(np.random.choice(nA, size=post, replace=True)).to(self.device)
                 rois[:, 1:].copy_(boxes[idx])
-            n = post
             nkeep = None
         elif str(cfg.TEST.MODE) == 'nms':
             pre = int(cfg.TEST.RPN_PRE_NMS_TOP_N); post = int(cfg.TEST.RPN_POST_NMS_TOP_N)
@@ -1072,26 +1093,37 @@ class resnetv1(Network):
             O.nms(sb, pre, float(cfg.TEST.RPN_NMS_THRESH), 0 if cfg.NMS_CMP == 'ge' else 1, post, nms_ws, keep, nkeep)
             rois = self.buf('tprop.rois', (post, 5), f32, zero=True); rsc = self.buf('tprop.rsc', (post,), f32)
             O.gather_rois(sb, ss, keep, nkeep, post, rois, rsc)
-            n = int(nkeep.item())                               # TEST mode returns host arrays anyway (NET:691-697)
         else:
             raise NotImplementedError(cfg.TEST.MODE)            # NET:265-266
-        n_own = n
         own = rois
+        n_forced = None
         if self.parity is not None and self.parity.get('forced_proposals') is not None:
             fr, _ = self.parity['forced_proposals']
             rois = self.buf('tprop.rois_forced', (post, 5), f32, zero=True)
-            rois[:fr.shape[0]].copy_(fr); n = int(fr.shape[0])
-        # heads run on all `post` slots (static shapes); rows >= n are padding and sliced off
+            rois[:fr.shape[0]].copy_(fr); n_forced = int(fr.shape[0])
+        # heads run on all `post` slots (static shapes); rows >= nkeep are padding
         cheads, cls_prob, bbox_pred, mprob = self._roi_heads_test(net_conv, Hc, Wc, rois, post)
+        return dict(net_conv=net_conv, net_conv_hw=(Hc, Wc), response=resp, rois=rois, own_rois=own, nkeep=nkeep, n_forced=n_forced, post=post,
+                    cheads=cheads, cls_prob=cls_prob, bbox_pred=bbox_pred, mask_prob=mprob, rpn_cls_prob=prob)
+
+    def forward_test(self, d):
+        """NET:628-662 with mode == 'TEST'.  Fills self._predictions like the reference (device tensors, NHWC / row-major)."""
+        self.forward_test_image(d)
+        s = self.forward_test_sentence(d)
+        post, nkeep = s['post'], s['nkeep']
+        n = post if nkeep is None else int(nkeep.item())        # TEST mode returns host arrays anyway (NET:691-697)
+        n_own = n
+        if s['n_forced'] is not None:
+            n = s['n_forced']
         nc = self._num_classes; MS = int(cfg.MASK_SIZE)
-        if mprob is None:                                   # VGG16 / Faster R-CNN network: no mask branch (network_vgg.py:614)
-            self._predictions = dict(net_conv=net_conv, net_conv_hw=(Hc, Wc), response=resp, rois=rois[:n], own_rois=own[:n_own],
-                                     cls_score=cheads[:n, :nc], cls_prob=cls_prob[:n], bbox_pred=bbox_pred[:n], rpn_cls_prob=prob)
-            return self._predictions
-        self._predictions = dict(net_conv=net_conv, net_conv_hw=(Hc, Wc), response=resp, rois=rois[:n], own_rois=own[:n_own],
-                                 cls_score=cheads[:n, :nc], cls_prob=cls_prob[:n], bbox_pred=bbox_pred[:n],
-                                 mask_prob=mprob.view(post, MS, MS, nc)[:n], rpn_cls_prob=prob)
-        return self._predictions
+        rois, own, cheads, mprob = s['rois'], s['own_rois'], s['cheads'], s['mask_prob']
+        p = dict(net_conv=s['net_conv'], net_conv_hw=s['net_conv_hw'], response=s['response'], rois=rois[:n], own_rois=own[:n_own],
+                 cls_score=cheads[:n, :nc], cls_prob=s['cls_prob'][:n], bbox_pred=s['bbox_pred'][:n])
+        if mprob is not None:                                   # (VGG16 / Faster R-CNN network: no mask branch, network_vgg.py:614)
+            p['mask_prob'] = mprob.view(post, MS, MS, nc)[:n]
+        p['rpn_cls_prob'] = s['rpn_cls_prob']
+        self._predictions = p
+        return p
 
     def test_image(self, blobs):
         """NET:684-699: (cls_score, cls_prob, bbox_pred, rois) as float32 ndarrays + net_conv (device tensor [H*W][1024], see
@@ -1109,6 +1141,11 @@ class resnetv1(Network):
         rois = torch.from_numpy(np.hstack([np.zeros((n, 1)), boxes]).astype(np.float32)).to(self.device)
         lab = torch.from_numpy(np.asarray(labels).astype(np.int32)).to(self.device)
         return self._roi_heads_test(net_conv, Hc, Wc, rois, n, labels=lab)[3]
+
+    def predict_mask_device(self, net_conv, Hc, Wc, roi, label):
+        """_predict_masks_from_boxes_and_labels for one box already on the device: roi float32 [1][5], label int32 [1] -> (1,14,14)"""
+        assert not self.training, 'only support testing mode'
+        return self._roi_heads_test(net_conv, Hc, Wc, roi, 1, labels=label)[3]
 
     def _consts(self):
         if not hasattr(self, '_cst'):

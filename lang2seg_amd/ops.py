@@ -519,6 +519,34 @@ def rle_to_mask(cnts, offs, n, total, h, w, ws, out):
     call('l2s_rle_to_mask', ptr(cnts), ptr(offs), n, total, h, w, out.shape[0], out.shape[1], ptr(ws), ptr(out), stream())
 
 
+EVAL_RECORD_BYTES = 48      # l2s_eval_record: roi, cls (int32), box[4] (f32), hit, reserved (int32), I, U (int64)
+
+
+def eval_records(n, device='cuda'):
+    """a zeroed device array of n l2s_eval_record (int64 [n][6]; eval_record_fields() reads it on the host)"""
+    return torch.zeros((n, EVAL_RECORD_BYTES // 8), dtype=torch.int64, device=device)
+
+
+def eval_record_fields(rec):
+    """host int64 [n][6] records -> (roi, cls, box [n][4] f32, hit, I, U) numpy arrays"""
+    a = rec.numpy() if isinstance(rec, torch.Tensor) else rec
+    i32 = a.view('<i4').reshape(a.shape[0], -1)
+    return i32[:, 0], i32[:, 1], i32[:, 2:6].view('<f4'), i32[:, 6], a[:, 4], a[:, 5]
+
+
+def eval_pick(cls_prob, bbox_pred, rois, nkeep, post, ncls, im_scale, im_h, im_w, gt_box, bbox_reg, rec, i, mask_roi, mask_label):
+    """model/test.py best_detection + detect_from_outputs + computeIoU_box on the device -> record i of `rec`, the mask head's RoI / label"""
+    call('l2s_eval_pick', ptr(cls_prob), ptr(bbox_pred), ptr(rois), ptr(nkeep), post, ncls, float(im_scale), im_h, im_w, ptr(gt_box),
+         1 if bbox_reg else 0, ptr(rec) + i * EVAL_RECORD_BYTES, ptr(mask_roi), ptr(mask_label), stream())
+
+
+def eval_mask_iou(mask_prob, rec, i, gt, ih, iw, canvas=None):
+    """segment_from_mask_prob + nearest gt resize + computeIoU_seg on the device: adds I, U to record i (gt: uint8 [Hs][Ws])"""
+    ms = mask_prob.shape[-1]
+    call('l2s_eval_mask_iou', ptr(mask_prob), ms, ptr(rec) + i * EVAL_RECORD_BYTES, ptr(gt), gt.shape[-2], gt.shape[-1], ih, iw,
+         ptr(canvas), stream())
+
+
 def rcnn_predict(heads, ldh, R, ncls, stds4, means4, cls_prob, bbox_pred):
     call('l2s_rcnn_predict', ptr(heads), ldh, R, ncls, ptr(stds4), ptr(means4), ptr(cls_prob), ptr(bbox_pred), stream())
 

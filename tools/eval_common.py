@@ -24,6 +24,8 @@ def parse_args(argv=None):
     p.add_argument('--results_dir', default=None, help='where det_results.txt / mask_results.txt are appended (default: experiments/)')
     p.add_argument('--synthetic', type=int, default=0, help='1: evaluate on the SyntheticLoader when the dataset files are absent')
     p.add_argument('--allow_init_weights', type=int, default=0, help='1: evaluate the initial weights when the snapshot is missing (otherwise an error)')
+    p.add_argument('--device_eval', type=int, default=0, help='1: model/eval_device.py (one backbone pass per image, metrics on the GPU, '
+                   'sharded over RANK / WORLD_SIZE); 0: the host loop model/test.py')
     return vars(p.parse_args(argv))
 
 
@@ -34,7 +36,10 @@ def main(args, variant):
     from lang2seg_amd.loaders.synthetic_loader import SyntheticLoader
     sys.path.insert(0, osp.join(ROOT, 'tools'))
     from opt import parse_opt
-    torch.cuda.set_device(0)
+    rank = int(os.environ.get('RANK', 0)); world = int(os.environ.get('WORLD_SIZE', 1)); local = int(os.environ.get('LOCAL_RANK', 0))
+    if world > 1 and not args['device_eval']:
+        raise ValueError('WORLD_SIZE > 1 evaluates through --device_eval 1 only')
+    torch.cuda.set_device(local % max(torch.cuda.device_count(), 1))
     T = 20 if args['dataset'] == 'refcocog' else 10
     V = 3349 if args['dataset'] == 'refcocog' else 1999
     data_json = osp.join(ROOT, 'cache/prepro', args['dataset'] + '_' + args['splitBy'], 'data.json')       # eval_cycle.py:45-48
@@ -54,6 +59,8 @@ def main(args, variant):
     if args['set_cfgs']:
         cfg_from_list(args['set_cfgs'])
     cfg.COMPUTE_DTYPE = args['dtype']
+    if world > 1:
+        torch.distributed.init_process_group(cfg.TRAIN.DP_BACKEND)
     if variant == 'vgg':
         from lang2seg_amd.nets.vgg16 import vgg16
         opt['C4_feat_dim'] = 512
@@ -73,12 +80,26 @@ def main(args, variant):
     split = args['split'] if args['split'] in loader.split_ix else 'val'
     if variant == 'vgg':                                     # tools/eval_vgg.py: boxes only (model/test_vgg.py)
         from lang2seg_amd.model.test_vgg import eval_split as eval_split_vgg
-        acc, n = eval_split_vgg(loader, net, None, split, dict(num_sents=args['num_sents'], verbose=bool(args['verbose'])))
+        eopt = dict(num_sents=args['num_sents'], verbose=bool(args['verbose']))
+        if args['device_eval']:
+            from lang2seg_amd.model.eval_device import eval_split_vgg_device
+            acc, n = eval_split_vgg_device(loader, net, None, split, eopt, rank=rank, world=world)
+        else:
+            acc, n = eval_split_vgg(loader, net, None, split, eopt)
+        if rank != 0:
+            return acc, None, None
         print('Comprehension on %s\'s %s (%s sents): box acc %.2f%%' % (opt['dataset_splitBy'], args['split'], n, acc * 100))
         return acc, None, None
     opt['split'], opt['id'] = args['split'], args['id']
-    acc, eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U, num_sent = eval_split(
-        loader, net, None, split, dict(num_sents=args['num_sents'], verbose=bool(args['verbose'])))
+    eopt = dict(num_sents=args['num_sents'], verbose=bool(args['verbose']))
+    if args['device_eval']:
+        from lang2seg_amd.model.eval_device import eval_split_device
+        res = eval_split_device(loader, net, None, split, eopt, rank=rank, world=world)
+    else:
+        res = eval_split(loader, net, None, split, eopt)
+    acc, eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U, num_sent = res
+    if rank != 0:                                            # the totals are the same on every rank; rank 0 prints and writes the logs
+        return acc, None, None
     print('Comprehension on %s\'s %s (%s sents) is %.2f%%' % (opt['dataset_splitBy'], split, num_sent, acc * 100.))
     results_str, prec, iou = summarize(eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U)
     print('Segmentation results on [%s][%s]' % (opt['dataset_splitBy'], split))
