@@ -555,53 +555,73 @@ class resnetv1(Network):
             O.roialign_bwd(g, Hc, Wc, C4, rois, R, CS, 1.0 / 16.0, d_nc_roi)
         return d_nc_roi
 
-    def _roi_head_fwd(self, net_conv, Hc, Wc, rois, R, FGM, saved):
-        """RoI head (NET:572-586): crop-pool -> layer4 -> average -> (cls | bbox) heads, mask head on the first FGM RoI slots.
-        Returns (heads [R][NPC] f32, NPC, mask scores or None)."""
-        P, dt, t = self.P, self.dt, self.t
-        C4, nc = self._C4_feat_dim, self._num_classes
-        PS, MS = int(cfg.POOLING_SIZE), int(cfg.MASK_SIZE)
+    def _roi_trunk_fwd(self, net_conv, Hc, Wc, rois, n, saved=None):
+        """RoI head trunk of the train step and of TEST mode (NET:572-580): crop-pool -> layer4 -> average -> (cls | bbox) heads on
+        `n` rois [n][5].  saved: the train step's record for the backward pass; None in TEST mode, whose layer4 runs on buffers of its
+        own ('l4t').  Returns (heads [n][NPC] f32, layer4's output [n*PS*PS][2048]: the mask head's input)."""
+        P, dt = self.P, self.dt
+        C4, PS = self._C4_feat_dim, int(cfg.POOLING_SIZE)
+        train = saved is not None
+        tag = 'l4r' if train else 'l4t'
+        saved = saved if train else {}
         blk0 = self.layers[4][0]
         kind, CS, mp = self._pool_mode()
-        fused = (self.fuse_roialign and dt == BF16 and kind == 'crop' and not mp and blk0.down is not None and blk0.stride == 1 and
+        fused = (train and self.fuse_roialign and dt == BF16 and kind == 'crop' and not mp and blk0.down is not None and blk0.stride == 1 and
                  O.roialign_block0_ok(C4, PS, blk0.planes, blk0.planes * 4))
         if fused:
             # crop-and-resize + layer4[0].conv1 + layer4[0].downsample in one launch, one workgroup per RoI; the crop is still written
             # (once) for the weight gradients and the backward pass
-            pool5 = self.buf('roi.pool5', (R * PS * PS, C4))
-            a1 = self.buf('l4r.0.a1', (R * PS * PS, blk0.planes)); sc = self.buf('l4r.0.sc', (R * PS * PS, blk0.planes * 4))
-            O.roialign_block0_fwd(net_conv, Hc, Wc, C4, rois, R, PS, 1.0 / 16.0, blk0.c1.wf, blk0.c1.bias, blk0.planes,
+            pool5 = self.buf('roi.pool5', (n * PS * PS, C4))
+            a1 = self.buf('l4r.0.a1', (n * PS * PS, blk0.planes)); sc = self.buf('l4r.0.sc', (n * PS * PS, blk0.planes * 4))
+            O.roialign_block0_fwd(net_conv, Hc, Wc, C4, rois, n, PS, 1.0 / 16.0, blk0.c1.wf, blk0.c1.bias, blk0.planes,
                                   blk0.down.wf, blk0.down.bias, blk0.planes * 4, pool5, a1, sc)
-            x, hh, ww, sv = blk0.fwd_rest(pool5, a1, sc, R, PS, PS, 'l4r.0')
+            x, hh, ww, sv = blk0.fwd_rest(pool5, a1, sc, n, PS, PS, 'l4r.0')
             saved[('4r', 0)] = sv
         else:
-            pool5 = self._rois_pool_fwd(net_conv, Hc, Wc, rois, R, saved)
+            pool5 = self._rois_pool_fwd(net_conv, Hc, Wc, rois, n, saved)
             x, hh, ww = pool5, PS, PS
         for b, blk in enumerate(self.layers[4]):
             if fused and b == 0:
                 continue
-            x, hh, ww, sv = blk.fwd(x, R, hh, ww, 'l4r.%d' % b)
+            x, hh, ww, sv = blk.fwd(x, n, hh, ww, '%s.%d' % (tag, b))
             saved[('4r', b)] = sv
         fc7s = x
-        fc7 = self.buf('roi.fc7', (R, 2048))
-        O.avgpool_fwd(fc7s, fc7, R, PS * PS, 2048)
-        NPC = P.rcnn_npad
-        cheads = self.buf('roi.heads', (R, NPC), f32)
-        self.rcnn_heads.fwd(fc7, R, 1, 1, cheads, out_f32=True)
-        up = self.buf('mask.up', (FGM * MS * MS, 256))
-        O.conv_igemm(fc7s, self.up_wT, up, FGM, PS, PS, 2048, PS, PS, 4 * 256, bias=P.view('mask_up_sampling.bias'), relu=True, deconv=True, dt=dt)
-        mscore = self.buf('mask.score', (FGM * MS * MS, nc), f32)
-        self.mask_pred.fwd(up, FGM, MS, MS, mscore, out_f32=True)
-        t.update({'pool5': pool5, 'spatial_fc7': fc7s, 'rcnn_heads': cheads, 'mask_score': mscore})
-        saved['roi'] = (fc7s, fc7, up)
-        return cheads, NPC, mscore
+        fc7 = self.buf('roi.fc7', (n, 2048))
+        O.avgpool_fwd(fc7s, fc7, n, PS * PS, 2048)
+        cheads = self.buf('roi.heads', (n, P.rcnn_npad), f32)
+        self.rcnn_heads.fwd(fc7, n, 1, 1, cheads, out_f32=True)
+        if train:
+            self.t.update({'pool5': pool5, 'spatial_fc7': fc7s, 'rcnn_heads': cheads})
+            saved['roi'] = (fc7s, fc7)
+        return cheads, fc7s
+
+    def _mask_fwd(self, fc7s, n):
+        """mask head (NET:581-586) on the first n RoI slots of layer4's output: 2x2 up-sampling (ConvTranspose + ReLU) -> mask_pred.
+        Returns (up-sampled map [n*MS*MS][256], scores [n*MS*MS][nc] f32)."""
+        P = self.P
+        PS, MS = int(cfg.POOLING_SIZE), int(cfg.MASK_SIZE)
+        up = self.buf('mask.up', (n * MS * MS, 256))
+        O.conv_igemm(fc7s, self.up_wT, up, n, PS, PS, 2048, PS, PS, 4 * 256, bias=P.view('mask_up_sampling.bias'), relu=True, deconv=True, dt=self.dt)
+        mscore = self.buf('mask.score', (n * MS * MS, self._num_classes), f32)
+        self.mask_pred.fwd(up, n, MS, MS, mscore, out_f32=True)
+        return up, mscore
+
+    def _roi_head_fwd(self, net_conv, Hc, Wc, rois, R, FGM, saved):
+        """RoI head of the train step: the trunk on R RoI slots, the mask head on the first FGM.
+        Returns (heads [R][NPC] f32, mask scores or None: no mask branch)."""
+        cheads, fc7s = self._roi_trunk_fwd(net_conv, Hc, Wc, rois, R, saved)
+        if fc7s is None:
+            return cheads, None
+        saved['mask_up'], mscore = self._mask_fwd(fc7s, FGM)
+        self.t['mask_score'] = mscore
+        return cheads, mscore
 
     def _roi_head_bwd(self, d_cheads, dscore, labels, counts, rois, Hc, Wc, R, FGM, saved):
         """adjoint of _roi_head_fwd -> d(net_conv) [H*W][C4] f32 (RoIAlign scatter)."""
         P, dt = self.P, self.dt
         C4 = self._C4_feat_dim
         PS, MS = int(cfg.POOLING_SIZE), int(cfg.MASK_SIZE)
-        fc7s, fc7, up = saved['roi']
+        (fc7s, fc7), up = saved['roi'], saved['mask_up']
         HW = Hc * Wc
         # rcnn heads -> fc7 -> spatial_fc7
         self.rcnn_heads.wgrad(d_cheads, fc7, R, 1, 1)
@@ -629,6 +649,60 @@ class resnetv1(Network):
             g = self.layers[4][b].bwd(g, saved[('4r', b)], 'l4r.%d' % b, x_is_relu_out=(b > 0))
         self._mark('roi head bwd')
         return self._rois_pool_bwd(g, Hc, Wc, rois, R, saved)
+
+    # ------------------------------------------------------------------ forward stages of the train step and of TEST mode
+    def _filter_fwd(self, d):
+        """expression encoding (ENC:27-82) + the dynamic filters' linear layer -> filt [7 * C4 + 7]: the layout the correlation kernels
+        read, 7 filters [C4] + 7 mixing weights"""
+        P = self.P
+        C4 = self._C4_feat_dim
+        hidden = self._encoder_fwd(d)
+        HD = hidden.numel()
+        NF, NFP = 7 * C4 + 7, self._NFP
+        filt = self.buf('dyn.filt', (NF,), f32, zero=(NFP != NF))
+        O.linear_fwd(hidden, P.gview('dyn_w', NFP * HD), P.gview('dyn_b', NFP), filt, 1, NFP, HD, act=2)
+        if NFP != NF:
+            # baseline network (network.py:475-479): one filter, response = its correlation -> mixing weights (1,0,..,0)
+            if not hasattr(self, '_r_one'):
+                self._r_one = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], dtype=f32, device=self.device)
+            O.memcpy(filt[7 * C4:], self._r_one)
+        return filt
+
+    def _dynfilter_fwd(self, base, filt, Hc, Wc):
+        """dynamic filters (NET:504-562) -> (net_conv [H*W][C4], response [H*W] f32, per-filter responses [H*W][7] f32)"""
+        C4 = self._C4_feat_dim
+        net_conv = self.buf('dyn.y', (Hc * Wc, C4)); resp = self.buf('dyn.resp', (Hc * Wc,), f32); respk = self.buf('dyn.respk', (Hc * Wc, 7), f32)
+        O.dynfilter_fwd(base, filt, filt[7 * C4:], net_conv, resp, respk, Hc, Wc, C4, gate=1 if self.var['gate'] == 'sigmoid' else 0)
+        return net_conv, resp, respk
+
+    def _rpn_fwd(self, net_conv, Hc, Wc):
+        """RPN (NET:235-275): 3x3 conv -> (cls | bbox) heads -> softmax, anchor decoding and clipping to the image (self._im_hw).
+        Returns (conv output [H*W][512], heads [H*W][NPR] f32, cls prob [H*W][2A], boxes [H*W*A][4], fg scores [H*W*A])."""
+        A, HW, NPR = self._num_anchors, Hc * Wc, self.P.rpn_npad
+        rpn = self.buf('rpn.a', (HW, 512))
+        self.rpn_conv.fwd(net_conv, 1, Hc, Wc, rpn, relu=True)
+        rheads = self.buf('rpn.heads', (HW, NPR), f32)
+        self.rpn_heads.fwd(rpn, 1, Hc, Wc, rheads, out_f32=True)
+        nA = HW * A
+        prob = self.buf('rpn.prob', (HW, 2 * A), f32); boxes = self.buf('rpn.boxes', (nA, 4), f32); scores = self.buf('rpn.scores', (nA,), f32)
+        O.rpn_decode(rheads, NPR, self.base_anchors, Hc, Wc, A, 16, self._im_hw[0], self._im_hw[1], prob, boxes, scores)
+        return rpn, rheads, prob, boxes, scores
+
+    def _nms_proposals(self, scores, boxes, nA, key, pfx):
+        """proposal layer (PL:49-60) with the settings of cfg[key] ('TRAIN' / 'TEST') on buffers named pfx.*: the best RPN_PRE_NMS_TOP_N
+        of the nA boxes -> NMS -> the first RPN_POST_NMS_TOP_N kept.  Returns (rois [post][5], scores [post], device keep count [1] int32);
+        gather_rois writes every row, zeros past the keep count."""
+        c = cfg[key]
+        pre, post = int(c.RPN_PRE_NMS_TOP_N), int(c.RPN_POST_NMS_TOP_N)
+        pre = nA if pre <= 0 else min(pre, nA)
+        sb = self.buf(pfx + '.sb', (pre, 4), f32); ss = self.buf(pfx + '.ss', (pre,), f32); si = self.buf(pfx + '.si', (pre,), torch.int32)
+        O.sort_topk(scores, boxes, nA, pre, self.buf('prop.sortws', (O.sort_ws_ints(nA),), torch.int32), sb, ss, si)        # PL:49-53
+        nms_ws = self.buf(pfx + '.nmsws', (O.nms_workspace_bytes(pre) // 8 + 8,), torch.int64)
+        keep = self.buf(pfx + '.keep', (post,), torch.int32); nkeep = self.buf(pfx + '.nkeep', (1,), torch.int32)
+        O.nms(sb, pre, float(c.RPN_NMS_THRESH), 0 if cfg.NMS_CMP == 'ge' else 1, post, nms_ws, keep, nkeep)                 # PL:56-60
+        rois = self.buf(pfx + '.rois', (post, 5), f32); rsc = self.buf(pfx + '.rsc', (post,), f32)
+        O.gather_rois(sb, ss, keep, nkeep, post, rois, rsc)
+        return rois, rsc, nkeep
 
     # ------------------------------------------------------------------ the step
     keep_logprobs = False
@@ -675,29 +749,19 @@ class resnetv1(Network):
         # (DESIGN.md 4.7l).  The step counter (fresh RNG on every replay: every reader - dropout masks, sampling keys - runs on the language
         # stream, behind this launch), the clear of the loss accumulators and of the dynamic-filter gradient, the RoI sampling keys: all at
         # the head of the language stream, which the main queue joins before the dynamic filters.
-        post_ = int(cfg['TRAIN' if self._mode == 'TRAIN' else 'TEST'].RPN_POST_NMS_TOP_N)
+        key = 'TRAIN' if self._mode == 'TRAIN' else 'TEST'
+        post = int(cfg[key].RPN_POST_NMS_TOP_N)
+        n_gt = int(d['gt_boxes'].shape[0])
         with on('lang'):
             O.counter_inc(self.seed_counter())
             loss = self.buf('loss', (8,), f32, zero=True)
-            NF_ = 7 * C4 + 7
-            dfilt_ = self.buf('dyn.dfilt', (NF_,), f32, zero=True) if backward else None
-            n_gt_ = int(d['gt_boxes'].shape[0])
-            roi_keys = (self._keys('roi_fg_keys', post_ + n_gt_), self._keys('roi_bg_keys', post_ + n_gt_), self._keys('roi_bg_rand', R))
+            dfilt_ = self.buf('dyn.dfilt', (7 * C4 + 7,), f32, zero=True) if backward else None
+            roi_keys = (self._keys('roi_fg_keys', post + n_gt), self._keys('roi_bg_keys', post + n_gt), self._keys('roi_bg_rand', R))
         if S is not None and self.update_on_wg:
             with torch.cuda.stream(S['lang']):
                 self.join_update(full=False)                # the encoder reads updated weights
         with on('lang'):
-            hidden = self._encoder_fwd(d)
-            HD = hidden.numel()
-            NF = 7 * C4 + 7                      # layout the correlation kernels read: 7 filters [C4] + 7 mixing weights
-            NFP = self._NFP
-            filt = self.buf('dyn.filt', (NF,), f32, zero=(NFP != NF))
-            O.linear_fwd(hidden, P.gview('dyn_w', NFP * HD), P.gview('dyn_b', NFP), filt, 1, NFP, HD, act=2)
-            if NFP != NF:
-                # baseline network (network.py:475-479): one filter, response = its correlation -> mixing weights (1,0,..,0)
-                if not hasattr(self, '_r_one'):
-                    self._r_one = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], dtype=f32, device=self.device)
-                O.memcpy(filt[7 * C4:], self._r_one)
+            filt = self._filter_fwd(d)
             # the pieces of the captioner that depend only on the tokens and the RNG counter (dropout masks, word embedding, i2h sums, the
             # zeroed backward buffer): off the caption branch's dependent chain, which is the step's critical path
             self._cap_pre = self._caption_pre(d) if (self.var['cap'] is not None and 'cap' not in self.knockout) else None
@@ -725,10 +789,9 @@ class resnetv1(Network):
                         x_, a1_, a2_, IH_, IW_, OH_, OW_, n_ = saved[(li, 0)]
                         O.memset_zero(self.buf('l%d.0.dx' % li, (n_ * IH_ * IW_, blk.inpl)))
                         self._precleared.add('l%d.0' % li)
-        net_conv = self.buf('dyn.y', (HW, C4)); resp = self.buf('dyn.resp', (HW,), f32); respk = self.buf('dyn.respk', (HW, 7), f32)
-        gate = 1 if self.var['gate'] == 'sigmoid' else 0
-        O.dynfilter_fwd(base, filt, filt[7 * C4:], net_conv, resp, respk, Hc, Wc, C4, gate=gate)
+        net_conv, resp, respk = self._dynfilter_fwd(base, filt, Hc, Wc)
         t['net_conv'], t['response'] = net_conv, resp
+        gate = 1 if self.var['gate'] == 'sigmoid' else 0
         dresp_extra = None
         if gate:
             # response loss (network_cycle_response.py:415-423) and its gradient w.r.t. the raw response
@@ -828,26 +891,11 @@ class resnetv1(Network):
         cap_advance()                                         # layer4 on the map + pooled caption features
         self._mark('dyn + caption branch (cap)')
         # ---- RPN (NET:235-275) ----
-        rpn = self.buf('rpn.a', (HW, 512))
-        self.rpn_conv.fwd(net_conv, 1, Hc, Wc, rpn, relu=True)
-        NPR = P.rpn_npad
-        rheads = self.buf('rpn.heads', (HW, NPR), f32)
-        self.rpn_heads.fwd(rpn, 1, Hc, Wc, rheads, out_f32=True)
-        nA = HW * A
-        prob = self.buf('rpn.prob', (HW, 2 * A), f32); boxes = self.buf('rpn.boxes', (nA, 4), f32); scores = self.buf('rpn.scores', (nA,), f32)
-        O.rpn_decode(rheads, NPR, self.base_anchors, Hc, Wc, A, 16, im_h, im_w, prob, boxes, scores)
+        rpn, rheads, prob, boxes, scores = self._rpn_fwd(net_conv, Hc, Wc)
+        NPR, nA = P.rpn_npad, HW * A
         t['rpn_heads'], t['rpn_cls_prob'] = rheads, prob
         self._mark('rpn conv+heads+decode')
-        key = 'TRAIN' if self._mode == 'TRAIN' else 'TEST'
-        pre = int(cfg[key].RPN_PRE_NMS_TOP_N); post = int(cfg[key].RPN_POST_NMS_TOP_N)
-        pre = nA if pre <= 0 else min(pre, nA)
-        sb = self.buf('prop.sb', (pre, 4), f32); ss = self.buf('prop.ss', (pre,), f32); si = self.buf('prop.si', (pre,), torch.int32)
-        O.sort_topk(scores, boxes, nA, pre, self.buf('prop.sortws', (O.sort_ws_ints(nA),), torch.int32), sb, ss, si)                                      # PL:49-53
-        nms_ws = self.buf('prop.nmsws', (O.nms_workspace_bytes(pre) // 8 + 8,), torch.int64)
-        keep = self.buf('prop.keep', (post,), torch.int32); nkeep = self.buf('prop.nkeep', (1,), torch.int32)
-        O.nms(sb, pre, float(cfg[key].RPN_NMS_THRESH), 0 if cfg.NMS_CMP == 'ge' else 1, post, nms_ws, keep, nkeep)   # PL:56-60
-        rois_all = self.buf('prop.rois', (post, 5), f32); rsc_all = self.buf('prop.rsc', (post,), f32)
-        O.gather_rois(sb, ss, keep, nkeep, post, rois_all, rsc_all)
+        rois_all, rsc_all, nkeep = self._nms_proposals(scores, boxes, nA, key, 'prop')
         t['proposal_rois'], t['proposal_n'], t['proposal_scores'] = rois_all, nkeep, rsc_all
         cap_advance()                                         # captioner forward
         if self.parity is not None and self.parity.get('forced_proposals') is not None:
@@ -861,7 +909,6 @@ class resnetv1(Network):
         rl = self.buf('atl.labels', (nA,), torch.int32); rt = self.buf('atl.t', (HW, 4 * A), f32)
         ri = self.buf('atl.i', (HW, 4 * A), f32); ro = self.buf('atl.o', (HW, 4 * A), f32)
         aws = self.buf('atl.ws', (O.anchor_target_ws_ints(nA),), torch.int32)
-        n_gt = int(d['gt_boxes'].shape[0])
         if S is not None:
             self.sfork(main, S['lang'])
         with on('lang'):
@@ -892,15 +939,15 @@ class resnetv1(Network):
         mt = self.buf('ptl.mt', (FGM, MS * MS), f32); counts = self.buf('ptl.counts', (4,), torch.int32)
         pws = self.buf('ptl.ws', (4 * (post + n_gt) + R + 16,), torch.int32)
         cst = self._consts()
-        assert post == post_ and n_gt == n_gt_
         O.proposal_target(rois_all, rsc_all, nkeep, post, d['gt_boxes'], n_gt, d['gt_masks'], H, W, roi_keys[0],
                           roi_keys[1], roi_keys[2], R, FGS, FGM, TR.FG_THRESH, TR.BG_THRESH_HI,
                           TR.BG_THRESH_LO, cst['means'], cst['stds'], cst['inw'], nc, MS, rois, labels, bt, bi, bo, mt, counts, pws)
         t.update({'rois': rois, 'labels': labels, 'bbox_targets': bt, 'bbox_inside': bi, 'bbox_outside': bo, 'mask_targets': mt, 'counts': counts})
         self._mark('targets')
         self.conv_algo = 7 if self.roi_pdma else None       # (L2S_ALGO_PDMA)
-        cheads, NPC, mscore = self._roi_head_fwd(net_conv, Hc, Wc, rois, R, FGM, saved)
+        cheads, mscore = self._roi_head_fwd(net_conv, Hc, Wc, rois, R, FGM, saved)
         self.conv_algo = None
+        NPC = P.rcnn_npad
         self._mark('roi head fwd')
         cap_advance()                                         # captioner backward
         # ---- detection losses + head gradients (NET:375-413) ----
@@ -963,6 +1010,8 @@ class resnetv1(Network):
             O.total_loss(loss, self._cap_loss_weight)
             O.dynfilter_bwd_finish(dresp_ws, respk, dfilt, dfilt[7 * C4:], Hc, Wc, C4)
             O.act_bwd(dfilt, filt, 2)
+            hidden, NFP = t['hidden'], self._NFP
+            HD = hidden.numel()
             O.linear_bwd_w(dfilt, hidden, P.gview('dyn_w', NFP * HD, P.grad), P.gview('dyn_b', NFP, P.grad), 1, NFP, HD)
             dhidden = self.buf('enc.dhidden', (HD,), f32)
             nws = O.linear_bwd_x_ws_floats(1, NFP, HD)
@@ -980,63 +1029,22 @@ class resnetv1(Network):
 
 
     # ------------------------------------------------------------------ TEST mode (NET:488-593 mode == 'TEST', 595-626, 650-658)
-    def _test_filter(self, d):
-        """expression encoding + the dynamic filters' linear layer (TEST mode) -> filt [7 * C4 + 7]"""
-        P = self.P
-        C4 = self._C4_feat_dim
-        hidden = self._encoder_fwd(d)
-        HD = hidden.numel()
-        NF, NFP = 7 * C4 + 7, self._NFP
-        filt = self.buf('dyn.filt', (NF,), f32, zero=(NFP != NF))
-        O.linear_fwd(hidden, P.gview('dyn_w', NFP * HD), P.gview('dyn_b', NFP), filt, 1, NFP, HD, act=2)
-        if NFP != NF:
-            if not hasattr(self, '_r_one'):
-                self._r_one = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], dtype=f32, device=self.device)
-            O.memcpy(filt[7 * C4:], self._r_one)
-        return filt
-
-    def _test_dynfilter(self, filt, base, Hc, Wc):
-        C4 = self._C4_feat_dim
-        net_conv = self.buf('dyn.y', (Hc * Wc, C4)); resp = self.buf('dyn.resp', (Hc * Wc,), f32); respk = self.buf('dyn.respk', (Hc * Wc, 7), f32)
-        O.dynfilter_fwd(base, filt, filt[7 * C4:], net_conv, resp, respk, Hc, Wc, C4, gate=1 if self.var['gate'] == 'sigmoid' else 0)
-        return net_conv, resp
-
-    def _backbone_and_filter(self, d):
-        """conv1..layer3, expression encoding, dynamic filters -> (net_conv, base, Hc, Wc); single stream (inference)."""
-        self.join_update()
-        filt = self._test_filter(d)
-        base, Hc, Wc = self._backbone_fwd(d, {})
-        net_conv, resp = self._test_dynfilter(filt, base, Hc, Wc)
-        return net_conv, base, resp, Hc, Wc
-
     def _roi_heads_test(self, net_conv, Hc, Wc, rois, n, labels=None):
-        """crop-pool -> layer4 -> (cls scores, cls prob, de-normalised deltas) and mask probabilities for `n` rois [n][5]."""
-        P, dt = self.P, self.dt
-        C4, nc = self._C4_feat_dim, self._num_classes
-        PS, MS = int(cfg.POOLING_SIZE), int(cfg.MASK_SIZE)
-        pool5 = self._rois_pool_fwd(net_conv, Hc, Wc, rois, n, {})
-        x, hh, ww = pool5, PS, PS
-        for b, blk in enumerate(self.layers[4]):
-            x, hh, ww, _ = blk.fwd(x, n, hh, ww, 'l4t.%d' % b)
-        fc7s = x
-        fc7 = self.buf('roi.fc7', (n, 2048))
-        O.avgpool_fwd(fc7s, fc7, n, PS * PS, 2048)
-        NPC = P.rcnn_npad
-        cheads = self.buf('roi.heads', (n, NPC), f32)
-        self.rcnn_heads.fwd(fc7, n, 1, 1, cheads, out_f32=True)
+        """the RoI head trunk on `n` rois [n][5] -> (cls scores, cls prob, de-normalised deltas) and mask probabilities (None: no mask
+        branch, network_vgg.py:588-614); with `labels`, the probability map of each RoI's own class only."""
+        nc, MS = self._num_classes, int(cfg.MASK_SIZE)
+        cheads, fc7s = self._roi_trunk_fwd(net_conv, Hc, Wc, rois, n)
         cst = self._consts()
         cls_prob = self.buf('test.cls_prob', (n, nc), f32); bbox_pred = self.buf('test.bbox_pred', (n, 4 * nc), f32)
-        O.rcnn_predict(cheads, NPC, n, nc, cst['stds'], cst['means'], cls_prob, bbox_pred)
-        up = self.buf('mask.up', (n * MS * MS, 256))
-        O.conv_igemm(fc7s, self.up_wT, up, n, PS, PS, 2048, PS, PS, 4 * 256, bias=P.view('mask_up_sampling.bias'), relu=True, deconv=True, dt=dt)
-        mscore = self.buf('mask.score', (n * MS * MS, nc), f32)
-        self.mask_pred.fwd(up, n, MS, MS, mscore, out_f32=True)
+        O.rcnn_predict(cheads, self.P.rcnn_npad, n, nc, cst['stds'], cst['means'], cls_prob, bbox_pred)
+        if fc7s is None:
+            return cheads, cls_prob, bbox_pred, None
+        _, mscore = self._mask_fwd(fc7s, n)
         if labels is None:
             mprob = self.buf('test.mask_prob', (n * MS * MS, nc), f32)
-            O.mask_prob(mscore, nc, nc, None, MS * MS, n * MS * MS, mprob)
         else:
             mprob = self.buf('test.mask_prob_l', (n, MS, MS), f32)
-            O.mask_prob(mscore, nc, nc, labels, MS * MS, n * MS * MS, mprob)
+        O.mask_prob(mscore, nc, nc, labels, MS * MS, n * MS * MS, mprob)
         return cheads, cls_prob, bbox_pred, mprob
 
     def forward_test_image(self, d):
@@ -1053,23 +1061,13 @@ class resnetv1(Network):
         """the sentence half of the TEST forward on the backbone map of the last forward_test_image: expression encoding, dynamic filters,
         RPN, proposals and the heads on all `post` slots.  No host synchronisation (except TEST.MODE 'top' with fewer anchors than
         RPN_TOP_N, whose draw is numpy's): device buffers + the device keep count `nkeep` (None: all `post` rows are real)."""
-        A = self._num_anchors
-        im_h, im_w = float(d['im_info'][0]), float(d['im_info'][1])
-        self._im_hw = (im_h, im_w)
+        self._im_hw = (float(d['im_info'][0]), float(d['im_info'][1]))
         self.join_update()
-        filt = self._test_filter(d)
+        filt = self._filter_fwd(d)
         base, Hc, Wc = self._test_base
-        net_conv, resp = self._test_dynfilter(filt, base, Hc, Wc)
-        HW = Hc * Wc
-        P = self.P
-        rpn = self.buf('rpn.a', (HW, 512))
-        self.rpn_conv.fwd(net_conv, 1, Hc, Wc, rpn, relu=True)
-        NPR = P.rpn_npad
-        rheads = self.buf('rpn.heads', (HW, NPR), f32)
-        self.rpn_heads.fwd(rpn, 1, Hc, Wc, rheads, out_f32=True)
-        nA = HW * A
-        prob = self.buf('rpn.prob', (HW, 2 * A), f32); boxes = self.buf('rpn.boxes', (nA, 4), f32); scores = self.buf('rpn.scores', (nA,), f32)
-        O.rpn_decode(rheads, NPR, self.base_anchors, Hc, Wc, A, 16, im_h, im_w, prob, boxes, scores)
+        net_conv, resp, _ = self._dynfilter_fwd(base, filt, Hc, Wc)
+        _, _, prob, boxes, scores = self._rpn_fwd(net_conv, Hc, Wc)
+        nA = Hc * Wc * self._num_anchors
         if str(cfg.TEST.MODE) == 'top':
             # NET:263-264 -> proposal_top_layer.py:18-67: the RPN_TOP_N best anchors, decoded + clipped (rpn_decode did both), no NMS
             post = int(cfg.TEST.RPN_TOP_N)
@@ -1084,15 +1082,8 @@ class resnetv1(Network):
                 rois[:, 1:].copy_(boxes[idx])
             nkeep = None
         elif str(cfg.TEST.MODE) == 'nms':
-            pre = int(cfg.TEST.RPN_PRE_NMS_TOP_N); post = int(cfg.TEST.RPN_POST_NMS_TOP_N)
-            pre = nA if pre <= 0 else min(pre, nA)
-            sb = self.buf('tprop.sb', (pre, 4), f32); ss = self.buf('tprop.ss', (pre,), f32); si = self.buf('tprop.si', (pre,), torch.int32)
-            O.sort_topk(scores, boxes, nA, pre, self.buf('prop.sortws', (O.sort_ws_ints(nA),), torch.int32), sb, ss, si)
-            nms_ws = self.buf('tprop.nmsws', (O.nms_workspace_bytes(pre) // 8 + 8,), torch.int64)
-            keep = self.buf('tprop.keep', (post,), torch.int32); nkeep = self.buf('tprop.nkeep', (1,), torch.int32)
-            O.nms(sb, pre, float(cfg.TEST.RPN_NMS_THRESH), 0 if cfg.NMS_CMP == 'ge' else 1, post, nms_ws, keep, nkeep)
-            rois = self.buf('tprop.rois', (post, 5), f32, zero=True); rsc = self.buf('tprop.rsc', (post,), f32)
-            O.gather_rois(sb, ss, keep, nkeep, post, rois, rsc)
+            rois, _, nkeep = self._nms_proposals(scores, boxes, nA, 'TEST', 'tprop')
+            post = rois.shape[0]
         else:
             raise NotImplementedError(cfg.TEST.MODE)            # NET:265-266
         own = rois

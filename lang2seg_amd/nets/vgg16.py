@@ -168,46 +168,31 @@ class vgg16(resnetv1):
     def _crop_max_pool(self):
         return True                                       # network_vgg.py:139 _crop_pool_layer(bottom, rois, max_pool=True)
 
-    def _roi_head_fwd(self, net_conv, Hc, Wc, rois, R, FGM, saved):
-        P, t = self.P, self.t
-        C4, nc = self._C4_feat_dim, self._num_classes
-        PS = int(cfg.POOLING_SIZE)
-        pool5 = self._rois_pool_fwd(net_conv, Hc, Wc, rois, R, saved)      # 14x14 crop + 2x2 max pool (Network._crop_pool_layer default)
-        h6 = self.buf('roi.fc6', (R, 4096))
-        self.fc6.fwd(pool5, R, PS, PS, h6, relu=True)
-        d6 = self._drop('fc6', (R, 4096), 0.5)
-        h6d = h6
-        if d6 is not None:
-            h6d = self.buf('roi.fc6d', (R, 4096)); O.scale_mask(h6, d6, None, h6d)
-        h7 = self.buf('roi.fc7', (R, 4096))
-        self.fc7.fwd(h6d, R, 1, 1, h7, relu=True)
-        d7 = self._drop('fc7', (R, 4096), 0.5)
-        h7d = h7
-        if d7 is not None:
-            h7d = self.buf('roi.fc7d', (R, 4096)); O.scale_mask(h7, d7, None, h7d)
-        NPC = P.rcnn_npad
-        cheads = self.buf('roi.heads', (R, NPC), f32)
-        self.rcnn_heads.fwd(h7d, R, 1, 1, cheads, out_f32=True)
-        t.update({'pool5': pool5, 'rcnn_heads': cheads})
-        saved['roi'] = (pool5, h6, h6d, d6, h7, h7d, d7)
-        return cheads, NPC, None
-
-    def _roi_heads_test(self, net_conv, Hc, Wc, rois, n, labels=None):
-        """TEST mode (network_vgg.py:588-614): crop-pool -> fc6 -> fc7 -> class scores / probabilities / de-normalised deltas; no masks."""
+    def _roi_trunk_fwd(self, net_conv, Hc, Wc, rois, n, saved=None):
+        """crop-pool -> fc6 -> fc7 -> (cls | bbox) heads on `n` rois, dropout behind fc6 and fc7 while training (outside training
+        `_drop` returns None: the TEST form, network_vgg.py:588-614).  saved: as resnetv1._roi_trunk_fwd.  No mask branch: returns
+        (heads [n][NPC] f32, None)."""
         P = self.P
-        nc, PS = self._num_classes, int(cfg.POOLING_SIZE)
-        pool5 = self._rois_pool_fwd(net_conv, Hc, Wc, rois, n, {})
+        PS = int(cfg.POOLING_SIZE)
+        pool5 = self._rois_pool_fwd(net_conv, Hc, Wc, rois, n, {} if saved is None else saved)   # 14x14 crop + 2x2 max pool (Network._crop_pool_layer default)
         h6 = self.buf('roi.fc6', (n, 4096))
         self.fc6.fwd(pool5, n, PS, PS, h6, relu=True)
+        d6 = self._drop('fc6', (n, 4096), 0.5)
+        h6d = h6
+        if d6 is not None:
+            h6d = self.buf('roi.fc6d', (n, 4096)); O.scale_mask(h6, d6, None, h6d)
         h7 = self.buf('roi.fc7', (n, 4096))
-        self.fc7.fwd(h6, n, 1, 1, h7, relu=True)
-        NPC = P.rcnn_npad
-        cheads = self.buf('roi.heads', (n, NPC), f32)
-        self.rcnn_heads.fwd(h7, n, 1, 1, cheads, out_f32=True)
-        cst = self._consts()
-        cls_prob = self.buf('test.cls_prob', (n, nc), f32); bbox_pred = self.buf('test.bbox_pred', (n, 4 * nc), f32)
-        O.rcnn_predict(cheads, NPC, n, nc, cst['stds'], cst['means'], cls_prob, bbox_pred)
-        return cheads, cls_prob, bbox_pred, None
+        self.fc7.fwd(h6d, n, 1, 1, h7, relu=True)
+        d7 = self._drop('fc7', (n, 4096), 0.5)
+        h7d = h7
+        if d7 is not None:
+            h7d = self.buf('roi.fc7d', (n, 4096)); O.scale_mask(h7, d7, None, h7d)
+        cheads = self.buf('roi.heads', (n, P.rcnn_npad), f32)
+        self.rcnn_heads.fwd(h7d, n, 1, 1, cheads, out_f32=True)
+        if saved is not None:
+            self.t.update({'pool5': pool5, 'rcnn_heads': cheads})
+            saved['roi'] = (pool5, h6, h6d, d6, h7, h7d, d7)
+        return cheads, None
 
     def _predict_masks_from_boxes_and_labels(self, net_conv, boxes, labels):
         raise NotImplementedError('the VGG16 / Faster R-CNN network has no mask branch (network_vgg.py:614; model/test_vgg.py evaluates boxes only)')
