@@ -494,6 +494,21 @@ int l2s_eval_pick(const float* cls_prob, const float* bbox_pred, const float* ro
 int l2s_eval_mask_iou(const float* mask_prob, int ms, l2s_eval_record* rec, const uint8_t* gt, int Hs, int Ws, int ih, int iw,
                       uint8_t* canvas, hipStream_t s);
 
+/* Device.  rleEncode (pyutils/refer/external/maskApi.c:32-41) of one row-major uint8 [h][w] mask (nonzero = 1), the counterpart of
+ * l2s_rle_to_mask: runs over the column-major order, starting with a run of zeros (a leading 0 if the first pixel is set; an all-zero
+ * mask is the single count h * w).  The n counts go to pool[off .. off + n) with off = *cursor at entry, *cursor advances by n and
+ * *span = {off, n}: calls on one stream pack their outputs back to back without the host.  If off + n > pool_words nothing is written
+ * to pool, *cursor stays and *span = {-1, n}.  pool, cursor, span, ws are device memory; ws: l2s_rle_encode_ws_words(h, w) uint32.
+ * h * w < 2^31.  l2s_rle_encode_chunk_rows(): the rows of one column that one lane encodes (the decomposition's chunk, for tests). */
+typedef struct { int off; int n; } l2s_rle_span;
+long l2s_rle_encode_ws_words(int h, int w);
+int l2s_rle_encode_chunk_rows(void);
+int l2s_rle_from_mask(const uint8_t* mask, int h, int w, uint32_t* pool, int pool_words, int* cursor, l2s_rle_span* span, uint32_t* ws,
+                      hipStream_t s);
+/* Host.  Run lengths -> COCO compressed run-length string (rleToString, maskApi.c:203-215), the inverse of l2s_rle_from_string.
+ * Returns the length of the zero-terminated string written to out[0..max_chars), or -1 if it does not fit. */
+int l2s_rle_to_string(const uint32_t* cnts, int n, char* out, int max_chars);
+
 /* ---------------------------------------------------------------- launch tape / streams ----- */
 /* `to` waits (device side) for everything enqueued so far on `from`; fork or join of the step's branches */
 int l2s_stream_fork(hipStream_t from, hipStream_t to);

@@ -5,7 +5,11 @@ pick kernel (csrc/eval.hip l2s_eval_pick: best_detection + detect_from_outputs +
 box and the mask / IoU kernel (l2s_eval_mask_iou: segment_from_mask_prob + nearest gt resize + computeIoU_seg).  Each sentence
 leaves one fixed-size record in a device array; the host reads the records once and reduces them with eval_split's own
 expressions, so the metrics are the host loop's by construction.  With world > 1, rank r takes the images at positions
-p = r (mod world) of the split and the integer totals are summed with one all_reduce."""
+p = r (mod world) of the split and the integer totals are summed with one all_reduce.
+
+Predictions (opt-in, `predictions=[]`): the mask / IoU kernel also stores each sentence's canvas, l2s_rle_from_mask (csrc/rle_encode.hip)
+turns it into COCO run lengths in a per-image pool on the device, and one read-back per image brings the records, the spans and the
+used part of the pool to the host, where the counts become the `counts` string of the reference's mask.encode."""
 import numpy as np
 import torch
 
@@ -72,8 +76,64 @@ def _upload_image(net, data, n_sent):
     return img, lab_d, lens, box_d, gm             # (freeing g behind the launches is safe: the allocator reuses it in stream order)
 
 
-def _eval_image(net, data, n_sent, rec, base, with_masks):
-    """every sentence of one image through the device path; record base + i for sentence i.  No host synchronisation."""
+def rle_encode_host(mask):
+    """maskApi.c:32-41 rleEncode on a host [h][w] mask -> uint32 counts (the fallback of a sentence whose counts overflowed the pool)"""
+    t = np.asarray(mask).T.reshape(-1) != 0
+    pos = np.flatnonzero(t != np.concatenate([[False], t[:-1]]))
+    return np.diff(np.concatenate([[0], pos, [t.size]])).astype(np.uint32)
+
+
+class _Export(object):
+    """the device side of one image's predictions: S canvases, the run-length pool with its cursor and spans, the picked scores"""
+
+    def __init__(self, device, S, ih, iw, with_masks, pool_words=None):
+        self.S, self.ih, self.iw, self.with_masks = S, ih, iw, with_masks
+        # meta: the pool cursor, S spans (off, n), S float32 scores
+        self.meta = torch.zeros((1 + 3 * S,), dtype=torch.int32, device=device)
+        self.scores = self.meta[1 + 2 * S:].view(torch.float32)
+        if with_masks:
+            # a budget, not a bound: Pillow's BILINEAR upscale of MASK_SIZE rows crosses the threshold at most ~MASK_SIZE times per
+            # column (8651 counts for a 14 x 14 checkerboard over 640 x 640); a sentence beyond it is encoded on the host
+            words = S * (iw * (int(cfg.MASK_SIZE) + 2) + 2) if pool_words is None else int(pool_words)
+            self.canvas = torch.empty((S, ih, iw), dtype=torch.uint8, device=device)
+            self.pool = torch.empty((max(words, 1),), dtype=torch.int32, device=device)
+            self.ws = torch.empty((O.rle_encode_ws_words(ih, iw),), dtype=torch.int32, device=device)
+
+    def score(self, rec, k, i, cls_prob, C):
+        """cls_prob at the pick of record k, gathered behind the pick kernel (index 0 when nothing was picked)"""
+        r = rec.view(torch.int32).view(-1, O.EVAL_RECORD_BYTES // 4)[k]
+        idx = (r[0:1].to(torch.int64) * C + r[1:2]).clamp_(min=0)
+        self.scores[i:i + 1].copy_(cls_prob.reshape(-1).index_select(0, idx))
+
+    def encode(self, i):
+        O.rle_from_mask(self.canvas[i], self.pool, self.meta[0:1], self.meta[1 + 2 * i:3 + 2 * i], self.ws)
+
+    def collect(self, rec_h, file_name, gt=True):
+        """the read-back (meta, then the used prefix of the pool) -> one dict per sentence"""
+        S = self.S
+        meta = self.meta.cpu().numpy()
+        roi, cls, box, hit, Is, Us = O.eval_record_fields(rec_h)
+        scores = meta[1 + 2 * S:].view('<f4')
+        if self.with_masks:
+            pool = self.pool[:int(meta[0])].cpu().numpy().view('<u4')
+        out = []
+        for i in range(S):
+            p = dict(file_name=file_name, sent_index=i, category_id=int(cls[i]), box=[float(v) for v in box[i]], score=float(scores[i]))
+            if gt:
+                p.update(hit=int(hit[i]), I=int(Is[i]), U=int(Us[i]))
+            else:
+                p['area'] = int(Us[i])
+            if self.with_masks:
+                off, n = int(meta[1 + 2 * i]), int(meta[2 + 2 * i])
+                cnts = pool[off:off + n] if off >= 0 else rle_encode_host(self.canvas[i].cpu().numpy())
+                p['segmentation'] = dict(size=[self.ih, self.iw], counts=O.rle_to_string(cnts))
+            out.append(p)
+        return out
+
+
+def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1):
+    """every sentence of one image through the device path; record base + i for sentence i.  No host synchronisation.
+    pool_words >= 0 or None: also keep the predictions on the device (None: the default pool budget) -> the image's _Export"""
     img, lab_d, lens, box_d, gm = _upload_image(net, data, n_sent)
     im_info = np.asarray(data['im_info'], dtype=np.float32).reshape(-1)[:3]
     scale, ih, iw = _geometry(im_info)
@@ -82,16 +142,22 @@ def _eval_image(net, data, n_sent, rec, base, with_masks):
     MS = int(cfg.MASK_SIZE)
     roi = net.buf('eval.mask_roi', (1, 5), torch.float32)
     lab = net.buf('eval.mask_label', (1,), torch.int32)
+    ex = None if pool_words == -1 else _Export(torch.device(net.device), n_sent, ih, iw, with_masks, pool_words)
     for i in range(n_sent):
         d['labels'] = lab_d[i, :lens[i]]
         d['T'] = lens[i]
         s = net.forward_test_sentence(d)
         O.eval_pick(s['cls_prob'], s['bbox_pred'], s['rois'], s['nkeep'], s['post'], net._num_classes, scale, ih, iw, box_d[i],
                     cfg.TEST.BBOX_REG, rec, base + i, roi, lab)
+        if ex is not None:
+            ex.score(rec, base + i, i, s['cls_prob'], net._num_classes)
         if with_masks:
             Hc, Wc = s['net_conv_hw']
             mprob = net.predict_mask_device(s['net_conv'], Hc, Wc, roi, lab).view(MS, MS)
-            O.eval_mask_iou(mprob, rec, base + i, gm[i], ih, iw)
+            O.eval_mask_iou(mprob, rec, base + i, gm[i], ih, iw, canvas=None if ex is None else ex.canvas[i])
+            if ex is not None:
+                ex.encode(i)
+    return ex
 
 
 class _Totals(object):
@@ -122,7 +188,7 @@ class _Totals(object):
                 details.append((int(roi[j]), int(cls[j]), box[j].copy(), int(hit[j]), int(Is[j]), int(Us[j])))
 
 
-def _run(loader, model, split, opt, rank, world, details, with_masks, progress):
+def _run(loader, model, split, opt, rank, world, details, with_masks, progress, predictions=None, pool_words=None):
     num_sents = opt.get('num_sents', -1)
     verbose = opt.get('verbose', True)
     if world > 1 and num_sents > 0:
@@ -144,9 +210,13 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress):
             if num_sents > 0:
                 n = min(n, num_sents - issued)
             rec = O.eval_records(n, device)
-            _eval_image(model, data, n, rec, 0, with_masks)
+            ex = _eval_image(model, data, n, rec, 0, with_masks, -1 if predictions is None else pool_words)
             chunks.append(rec)
             issued += n
+            if ex is not None:                                 # one read-back per image: records, spans and cursor, then the pool's used part
+                rec_h = rec.cpu()
+                predictions.extend(ex.collect(rec_h, data.get('file_name')))
+                chunks[-1] = rec_h
             if verbose:                                        # one host synchronisation per image, for the progress line
                 for r in chunks:
                     tot.add(r.cpu(), details, with_masks)
@@ -170,21 +240,25 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress):
     return tot
 
 
-def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=None):
+def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=None, predictions=None, _pool_words=None):
     """model/test.py eval_split on the device.  Returns its 7-tuple (acc, eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U,
-    num_sent).  details: a list that receives (pred_roi, pred_class, pred_box, hit, I, U) per sentence of this rank."""
+    num_sent).  details: a list that receives (pred_roi, pred_class, pred_box, hit, I, U) per sentence of this rank.
+    predictions: a list that receives one dict per sentence of this rank: file_name, sent_index (position in the image's test batch),
+    category_id, box [x1, y1, x2, y2] (original image), score, hit, I, U and segmentation {'size': [ih, iw], 'counts': COCO RLE string}.
+    (_pool_words: the run-length pool of an image in words instead of its default budget; checks of the host fallback.)"""
     def progress(data, t):
         b = data['bounds']
         print('evaluating [%s] ... image[%d/%d]\'s sents, det acc=%.2f%%, seg acc=%.2f%%, seg IoU=%.2f%%' % (
             split, b['it_pos_now'], b['it_max'], t.acc * 100.0 / max(t.loss_evals, 1), t.seg_correct[0] * 100.0 / max(t.seg_total, 1),
             t.cum_I * 100.0 / max(t.cum_U, 1)))
-    t = _run(loader, model, split, opt, rank, world, details, True, progress)
+    t = _run(loader, model, split, opt, rank, world, details, True, progress, predictions, _pool_words)
     return t.acc / t.loss_evals, EVAL_SEG_IOU_LIST, t.seg_correct, t.seg_total, t.cum_I, t.cum_U, t.num_sent
 
 
-def eval_split_vgg_device(loader, model, crit, split, opt, rank=0, world=1, details=None):
-    """model/test_vgg.py eval_split on the device (boxes only: the VGG16 network has no mask branch) -> (acc, num_sent)"""
+def eval_split_vgg_device(loader, model, crit, split, opt, rank=0, world=1, details=None, predictions=None):
+    """model/test_vgg.py eval_split on the device (boxes only: the VGG16 network has no mask branch) -> (acc, num_sent).
+    predictions: as in eval_split_device, without I, U's mask meaning and without `segmentation`"""
     def progress(data, t):
         print('evaluating [%s] ... sent %d, det acc=%.2f%%' % (split, t.loss_evals, t.acc * 100.0 / max(t.loss_evals, 1)))
-    t = _run(loader, model, split, opt, rank, world, details, False, progress)
+    t = _run(loader, model, split, opt, rank, world, details, False, progress, predictions)
     return t.acc * 1.0 / max(t.loss_evals, 1), t.loss_evals

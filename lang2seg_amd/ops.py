@@ -519,7 +519,48 @@ def rle_to_mask(cnts, offs, n, total, h, w, ws, out):
     call('l2s_rle_to_mask', ptr(cnts), ptr(offs), n, total, h, w, out.shape[0], out.shape[1], ptr(ws), ptr(out), stream())
 
 
-EVAL_RECORD_BYTES = 48      # l2s_eval_record: roi, cls (int32), box[4] (f32), hit, reserved (int32), I, U (int64)
+def rle_encode_ws_words(h, w):
+    return int(_lib.load().l2s_rle_encode_ws_words(int(h), int(w)))
+
+
+def rle_encode_chunk_rows():
+    return int(_lib.load().l2s_rle_encode_chunk_rows())
+
+
+def rle_from_mask(mask, pool, cursor, span, ws):
+    """mask uint8 [h][w] (device, nonzero = 1) -> its run lengths appended to `pool` (uint32) at *cursor (int32 [1]); span (int32 [2]) takes
+    (offset, n), or (-1, n needed) with pool and cursor untouched when they do not fit.  ws: rle_encode_ws_words(h, w) uint32.  No host sync."""
+    h, w = mask.shape[-2], mask.shape[-1]
+    if ws.numel() < rle_encode_ws_words(h, w):
+        raise ValueError('rle_from_mask: workspace of %d words, %d needed' % (ws.numel(), rle_encode_ws_words(h, w)))
+    call('l2s_rle_from_mask', ptr(mask), h, w, ptr(pool), pool.numel(), ptr(cursor), ptr(span), ptr(ws), stream())
+
+
+def rle_to_string(cnts):
+    """uint32 run lengths -> COCO compressed RLE string (host; maskApi.c:203-215)."""
+    import numpy as np
+    c = np.ascontiguousarray(cnts, dtype=np.uint32)
+    buf = C.create_string_buffer(7 * c.size + 1)               # a 32-bit difference takes at most 7 characters of 5 bits
+    m = _lib.load().l2s_rle_to_string(c.ctypes.data, c.size, buf, len(buf))
+    if m < 0:
+        raise ValueError('rle_to_string: buffer too small')
+    return buf.raw[:m].decode('ascii')
+
+
+def mask_to_rle(mask_dev):
+    """uint8 [h][w] device mask -> {'size': [h, w], 'counts': str}, the COCO form of the reference's mask.encode (one read-back)"""
+    h, w = int(mask_dev.shape[-2]), int(mask_dev.shape[-1])
+    dev = mask_dev.device
+    pool = torch.empty((h * w + 1,), dtype=torch.int32, device=dev)
+    cs = torch.zeros((3,), dtype=torch.int32, device=dev)      # cursor, span
+    ws = torch.empty((rle_encode_ws_words(h, w),), dtype=torch.int32, device=dev)
+    rle_from_mask(mask_dev.contiguous(), pool, cs[0:1], cs[1:3], ws)
+    off, n = (int(v) for v in cs[1:3].cpu())
+    assert off == 0, (off, n)
+    return dict(size=[h, w], counts=rle_to_string(pool[:n].cpu().numpy().view('<u4')))
+
+
+EVAL_RECORD_BYTES = 48     # l2s_eval_record: roi, cls (int32), box[4] (f32), hit, reserved (int32), I, U (int64)
 
 
 def eval_records(n, device='cuda'):

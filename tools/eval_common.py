@@ -26,7 +26,20 @@ def parse_args(argv=None):
     p.add_argument('--allow_init_weights', type=int, default=0, help='1: evaluate the initial weights when the snapshot is missing (otherwise an error)')
     p.add_argument('--device_eval', type=int, default=0, help='1: model/eval_device.py (one backbone pass per image, metrics on the GPU, '
                    'sharded over RANK / WORLD_SIZE); 0: the host loop model/test.py')
+    p.add_argument('--dump_predictions', default=None, help='with --device_eval 1: write every sentence\'s prediction (class, box, score, hit, '
+                   'I, U, COCO RLE mask) as one JSON list to this path (rank r of WORLD_SIZE > 1 writes PATH.rank<r>)')
     return vars(p.parse_args(argv))
+
+
+def dump_predictions(args, preds, rank, world):
+    """--dump_predictions: this rank's predictions as one JSON list"""
+    if preds is None:
+        return
+    import json
+    path = args['dump_predictions'] + ('.rank%d' % rank if world > 1 else '')
+    with open(path, 'w') as f:
+        json.dump(preds, f)
+    print('wrote %d predictions to %s' % (len(preds), path))
 
 
 def main(args, variant):
@@ -39,6 +52,9 @@ def main(args, variant):
     rank = int(os.environ.get('RANK', 0)); world = int(os.environ.get('WORLD_SIZE', 1)); local = int(os.environ.get('LOCAL_RANK', 0))
     if world > 1 and not args['device_eval']:
         raise ValueError('WORLD_SIZE > 1 evaluates through --device_eval 1 only')
+    if args.get('dump_predictions') and not args['device_eval']:
+        raise ValueError('--dump_predictions needs --device_eval 1 (the host loop keeps no predictions)')
+    preds = [] if args.get('dump_predictions') else None
     torch.cuda.set_device(local % max(torch.cuda.device_count(), 1))
     T = 20 if args['dataset'] == 'refcocog' else 10
     V = 3349 if args['dataset'] == 'refcocog' else 1999
@@ -83,7 +99,8 @@ def main(args, variant):
         eopt = dict(num_sents=args['num_sents'], verbose=bool(args['verbose']))
         if args['device_eval']:
             from lang2seg_amd.model.eval_device import eval_split_vgg_device
-            acc, n = eval_split_vgg_device(loader, net, None, split, eopt, rank=rank, world=world)
+            acc, n = eval_split_vgg_device(loader, net, None, split, eopt, rank=rank, world=world, predictions=preds)
+            dump_predictions(args, preds, rank, world)
         else:
             acc, n = eval_split_vgg(loader, net, None, split, eopt)
         if rank != 0:
@@ -94,7 +111,8 @@ def main(args, variant):
     eopt = dict(num_sents=args['num_sents'], verbose=bool(args['verbose']))
     if args['device_eval']:
         from lang2seg_amd.model.eval_device import eval_split_device
-        res = eval_split_device(loader, net, None, split, eopt, rank=rank, world=world)
+        res = eval_split_device(loader, net, None, split, eopt, rank=rank, world=world, predictions=preds)
+        dump_predictions(args, preds, rank, world)
     else:
         res = eval_split(loader, net, None, split, eopt)
     acc, eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U, num_sent = res
