@@ -505,9 +505,41 @@ long l2s_rle_encode_ws_words(int h, int w);
 int l2s_rle_encode_chunk_rows(void);
 int l2s_rle_from_mask(const uint8_t* mask, int h, int w, uint32_t* pool, int pool_words, int* cursor, l2s_rle_span* span, uint32_t* ws,
                       hipStream_t s);
+/* Device.  l2s_rle_from_mask for n row-major masks of one size (masks [n][h][w]) in the same three launches: the masks are taken in
+ * order, each with the pool / cursor / span contract above and its own spans[b]; masks at b >= *n_valid (device int) are skipped
+ * with spans[b] = {0, 0}.  The bytes left in pool, the spans and the cursor are those of *n_valid consecutive l2s_rle_from_mask
+ * calls.  ws: n * l2s_rle_encode_ws_words(h, w) uint32.  n <= 65535. */
+int l2s_rle_from_masks(const uint8_t* masks, int n, const int* n_valid, int h, int w, uint32_t* pool, int pool_words, int* cursor,
+                       l2s_rle_span* spans, uint32_t* ws, hipStream_t s);
 /* Host.  Run lengths -> COCO compressed run-length string (rleToString, maskApi.c:203-215), the inverse of l2s_rle_from_string.
  * Returns the length of the zero-terminated string written to out[0..max_chars), or -1 if it does not fit. */
 int l2s_rle_to_string(const uint32_t* cnts, int n, char* out, int max_chars);
+
+/* ---------------------------------------------------------------- every instance per sentence (model/detect_device.py) ----- */
+/* One detection, in a caller-owned device array (32 bytes): the RoI row and class, the box in the original image, cls_prob[roi][cls]
+ * and the number of set pixels of its mask (0 until l2s_detect_paste). */
+typedef struct { int roi; int cls; float box[4]; float score; int area; } l2s_det_record;
+/* Device, one workgroup per class.  The reference's test.py:268-283 on the inputs of l2s_eval_pick (same decode, bit for bit): for every
+ * class j >= 1 the rows < *nkeep with cls_prob[r][j] > thresh (a NaN score is no candidate), ordered by score descending with ties by
+ * lower row, through greedy NMS as cpu_nms (lib/nms/src/nms.c:35-63: areas with + 1, ovr >= nms_thresh suppresses; float32, separate
+ * roundings).  The kept (row, score, box) lists go to ws (l2s_detect_ws_bytes(post, ncls) bytes) for l2s_detect_select.  boxes_dump:
+ * optional float [post][ncls][4], every decoded box (checks).  post <= 5120, 2 <= ncls <= 1024; L2S_EINVAL otherwise. */
+size_t l2s_detect_ws_bytes(int post, int ncls);
+int l2s_detect_nms(const float* cls_prob, const float* bbox_pred, const float* rois, const int* nkeep, int post, int ncls, float im_scale,
+                   int im_h, int im_w, int bbox_reg, float thresh, float nms_thresh, void* ws, float* boxes_dump, hipStream_t s);
+/* Device, one workgroup.  test.py:285-297 on the lists l2s_detect_nms left in ws: with max_per_image > 0 and more survivors than that,
+ * image_thresh = the max_per_image-th largest surviving score (exact: a radix select over the scores' bits) and a detection stays iff
+ * score >= image_thresh (ties all stay); max_per_image <= 0: no limit.  The detections in class order (inside a class: score
+ * descending, ties by lower row) go to rec[0 .. written), the mask head's RoIs (batch index 0, box * im_scale) and labels to
+ * mask_rois [cap][5], mask_labels [cap]; count = {written = min(total, cap), total}.  Rows in [written, cap) are zeroed; nothing
+ * behind cap is written. */
+int l2s_detect_select(const void* ws, int post, int ncls, int max_per_image, float im_scale, l2s_det_record* rec, float* mask_rois,
+                      int* mask_labels, int cap, int* count, hipStream_t s);
+/* Device.  l2s_eval_mask_iou's paste (recover_masks: bytescale, Pillow 8-bit BILINEAR, paste, > 122) for every detection d < count[0]:
+ * mask_prob [cap][ms][ms] on rec[d].box into canvases [cap][ih][iw] (uint8 {0, 1}), the set pixels added to rec[d].area (integer
+ * atomics).  Detections d >= count[0] are skipped, their canvases untouched.  cap <= 65535. */
+int l2s_detect_paste(const float* mask_prob, int ms, l2s_det_record* rec, const int* count, int cap, int ih, int iw, uint8_t* canvases,
+                     hipStream_t s);
 
 /* ---------------------------------------------------------------- launch tape / streams ----- */
 /* `to` waits (device side) for everything enqueued so far on `from`; fork or join of the step's branches */

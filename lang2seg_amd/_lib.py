@@ -158,7 +158,12 @@ SIGS = {
     'l2s_rle_encode_ws_words': (i64, [i32, i32]),
     'l2s_rle_encode_chunk_rows': (i32, []),
     'l2s_rle_from_mask': (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp]),
+    'l2s_rle_from_masks': (i32, [vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp]),
     'l2s_rle_to_string': (i32, [vp, i32, C.c_char_p, i32]),
+    'l2s_detect_ws_bytes': (sz, [i32, i32]),
+    'l2s_detect_nms': (i32, [vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, f32, f32, vp, vp, vp]),
+    'l2s_detect_select': (i32, [vp, i32, i32, i32, f32, vp, vp, vp, i32, vp, vp]),
+    'l2s_detect_paste': (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp]),
     'l2s_lstm_step_fwd': (i32, [vp, i32, i32, vp]),
     'l2s_lstm_step_bwd': (i32, [vp, i32, i32, vp]),
     'l2s_rcnn_predict': (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),

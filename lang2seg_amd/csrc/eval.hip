@@ -8,68 +8,13 @@
 // numpy's float32 exp is not correctly rounded, the device takes float64 exp rounded to float32 (a few ulp apart at most).
 #include "common.h"
 #include "../../include/lang2seg_hip.h"
-#include "pil_resize.h"
+#include "eval_helpers.h"
 #include <climits>
 #include <cmath>
 
 namespace {
 
-// ---------------------------------------------------------------- helpers (host + device: one text for kernels and checks)
-struct EvalGeom {
-  int x, y, w, h;
-};
-// mask_utils.recover_masks on one float32 box: clip_np_boxes, then h = int(y2 - y1 + 1), w = int(x2 - x1 + 1), x = int(x1), y = int(y1)
-__host__ __device__ inline EvalGeom eval_box_geometry(const float* box, int ih, int iw) {
-#pragma clang fp contract(off)
-  const float xm = (float)(iw - 1), ym = (float)(ih - 1);
-  const float x1 = fmaxf(fminf(box[0], xm), 0.f), y1 = fmaxf(fminf(box[1], ym), 0.f);
-  const float x2 = fmaxf(fminf(box[2], xm), 0.f), y2 = fmaxf(fminf(box[3], ym), 0.f);
-  EvalGeom g;
-  const float fh = y2 - y1 + 1.f, fw = x2 - x1 + 1.f;
-  const bool ok = fh == fh && fw == fw && fh > 0.f && fw > 0.f;        // a NaN box pastes nothing
-  g.h = ok ? (int)fh : 0;
-  g.w = ok ? (int)fw : 0;
-  g.x = ok ? (int)x1 : 0;
-  g.y = ok ? (int)y1 : 0;
-  return g;
-}
-// mask *= 255. then scipy's bytescale in float32 (NumPy 2 keeps every step in float32): cscale = cmax - cmin (0 -> 1),
-// scale = 255 / cscale, (x - cmin) * scale, clip to [0, 255], + 0.5, truncate to uint8
-__host__ __device__ inline int eval_bytescale_one(float x255, float cmin, float scale) {
-#pragma clang fp contract(off)
-  float v = (x255 - cmin) * scale;
-  v = fminf(fmaxf(v, 0.f), 255.f);
-  v = v + 0.5f;
-  return (int)v;
-}
-__host__ __device__ inline float eval_bytescale_factor(float cmin, float cmax) {
-#pragma clang fp contract(off)
-  const float cscale = cmax - cmin;
-  return cscale == 0.f ? 255.f : 255.f / cscale;
-}
-// the horizontal pass of Pillow's two-pass resize for output column xx of a w-wide box: the uint8 intermediate of every source row
-// (src [ms][ms], row-major); a pass whose size does not change is skipped (need_horizontal)
-__host__ __device__ inline void eval_column(const uint8_t* src, int ms, int w, int xx, int* tmp) {
-  if (w == ms) {
-    for (int y = 0; y < ms; ++y) tmp[y] = src[y * ms + xx];
-    return;
-  }
-  PilTaps th;
-  pil_bilinear_taps(ms, w, xx, th);
-  for (int y = 0; y < ms; ++y) {
-    int ss = 1 << (L2S_PIL_PRECISION_BITS - 1);
-    for (int x = 0; x < th.n; ++x) ss += src[y * ms + th.xmin + x] * th.k[x];
-    tmp[y] = pil_clip8(ss);
-  }
-}
-// the vertical pass for output row yy (taps tv of that row, unused when h == ms)
-__host__ __device__ inline int eval_vertical(const int* tmp, int ms, int h, int yy, const PilTaps& tv) {
-  if (h == ms) return tmp[yy];
-  int ss = 1 << (L2S_PIL_PRECISION_BITS - 1);
-  for (int y = 0; y < tv.n; ++y) ss += tmp[tv.xmin + y] * tv.k[y];
-  return pil_clip8(ss);
-}
-
+// (the helpers shared with detect.hip - box geometry, bytescale, the two resize passes, the box decode - are in eval_helpers.h)
 // ---------------------------------------------------------------- l2s_eval_pick
 __global__ __launch_bounds__(256) void eval_pick_kernel(const float* cls_prob, const float* bbox_pred, const float* rois, const int* nkeep,
                                                         int post, int C, float im_scale, int im_h, int im_w, const float* gt_box, int bbox_reg,
@@ -115,20 +60,8 @@ __global__ __launch_bounds__(256) void eval_pick_kernel(const float* cls_prob, c
   }
   const int row = sidx[0] / C, cls = sidx[0] % C;
   // detect_from_outputs on the chosen row: boxes = rois[:, 1:5] / scale, bbox_transform_inv_np, _clip_boxes (all float32)
-  float b[4], o[4];
-  for (int k = 0; k < 4; ++k) b[k] = rois[(long)row * 5 + 1 + k] / im_scale;
-  if (bbox_reg) {
-    const float* d = bbox_pred + (long)row * 4 * C + 4 * cls;
-    const float widths = b[2] - b[0] + 1.f, heights = b[3] - b[1] + 1.f;
-    const float ctr_x = b[0] + 0.5f * widths, ctr_y = b[1] + 0.5f * heights;
-    const float pcx = d[0] * widths + ctr_x, pcy = d[1] * heights + ctr_y;
-    const float pw = (float)exp((double)d[2]) * widths, ph = (float)exp((double)d[3]) * heights;
-    o[0] = pcx - 0.5f * pw; o[1] = pcy - 0.5f * ph; o[2] = pcx + 0.5f * pw; o[3] = pcy + 0.5f * ph;
-    o[0] = fmaxf(o[0], 0.f); o[1] = fmaxf(o[1], 0.f);
-    o[2] = fminf(o[2], (float)(im_w - 1)); o[3] = fminf(o[3], (float)(im_h - 1));
-  } else {
-    for (int k = 0; k < 4; ++k) o[k] = b[k];
-  }
+  float o[4];
+  eval_decode_box(rois + (long)row * 5, bbox_pred ? bbox_pred + (long)row * 4 * C + 4 * cls : rois, im_scale, im_h, im_w, bbox_reg, o);
   // computeIoU_box(pred_box, gt_box / im_scale) >= 0.5 in float32, the host's order of operations
   float g[4];
   for (int k = 0; k < 4; ++k) g[k] = gt_box[k] / im_scale;
@@ -165,16 +98,7 @@ __global__ __launch_bounds__(256) void eval_mask_iou_kernel(const float* prob, i
   const bool valid = rec->roi >= 0;
   const EvalGeom g = eval_box_geometry(box, ih, iw);
   // bytescale of the 14 x 14 probabilities * 255 over their own [min, max]
-  const float x255 = t < mm ? prob[t] * 255.f : 0.f;
-  smin[t] = t < mm ? x255 : INFINITY;
-  smax[t] = t < mm ? x255 : -INFINITY;
-  __syncthreads();
-  for (int o = blockDim.x >> 1; o > 0; o >>= 1) {
-    if (t < o) { smin[t] = fminf(smin[t], smin[t + o]); smax[t] = fmaxf(smax[t], smax[t + o]); }
-    __syncthreads();
-  }
-  const float cmin = smin[0], scale = eval_bytescale_factor(cmin, smax[0]);
-  if (t < mm) src[t] = (uint8_t)eval_bytescale_one(x255, cmin, scale);
+  eval_bytescale_block(prob, mm, smin, smax, src);
   if (t < EVAL_ROWS) {
     const int r = r0 + t;
     ty[t] = r < ih ? pil_nearest_src(r, Hs, ih) : 0;

@@ -1,6 +1,7 @@
 // Output side of evaluation and prediction (model/eval_device.py, model/predict_device.py): the predicted canvas leaves the device as
 // COCO run lengths instead of pixels.
 //   l2s_rle_from_mask   device   pyutils/refer/external/maskApi.c:32-41 (rleEncode), the counterpart of l2s_rle_to_mask (data.hip)
+//   l2s_rle_from_masks  device   the same for n masks of one size in the same three launches (model/detect_device.py)
 //   l2s_rle_to_string   host     maskApi.c:203-215 (rleToString), the counterpart of l2s_rle_from_string
 //
 // rleEncode walks the mask in column-major order k = x * h + y and emits a count whenever p[k] != p[k - 1], with p[-1] = 0.  That test
@@ -29,9 +30,14 @@ struct RleWs {
   __host__ __device__ RleWs(uint32_t* ws, long nch) : hdr(ws), tlo(ws + 8), thi(ws + 8 + nch), cnt(ws + 8 + 2 * nch), last((int*)(ws + 8 + 3 * nch)) {}
 };
 
-__global__ __launch_bounds__(256) void rle_count_kernel(const uint8_t* mask, int h, int w, int nseg, uint32_t* ws) {
+// (count and write take the mask index in the grid's z: mask b is mask + b * h * w with its own ws_stride words of workspace; masks at
+// b >= *n_valid are skipped.  l2s_rle_from_mask is the grid of one mask with n_valid NULL.)
+__global__ __launch_bounds__(256) void rle_count_kernel(const uint8_t* mask, int h, int w, int nseg, uint32_t* ws, long ws_stride, const int* n_valid) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, seg = blockIdx.y;
   if (x >= w) return;
+  if (n_valid && (int)blockIdx.z >= *n_valid) return;
+  mask += (long)blockIdx.z * h * w;
+  ws += (long)blockIdx.z * ws_stride;
   const int r0 = seg * RLE_SEG, nr = min(RLE_SEG, h - r0);
   // the pixel before the chunk in column-major order: the row above, else the last row of the column to the left, else p[-1] = 0
   uint64_t prev = 0;
@@ -61,10 +67,9 @@ __device__ __forceinline__ void wave_scan(uint32_t& s, int& m) {
   }
 }
 
-__global__ __launch_bounds__(RLE_SCAN_T) void rle_scan_kernel(long nch, int hw, uint32_t* ws, uint32_t* pool, int pool_words, int* cursor,
-                                                              l2s_rle_span* span) {
-  __shared__ uint32_t wsum[RLE_SCAN_T / 64];
-  __shared__ int wmax[RLE_SCAN_T / 64];
+// the scan and the pool decision of one mask by one workgroup (wsum, wmax: its shared scratch, free again behind the scan's last barrier)
+__device__ __forceinline__ void rle_scan_one(long nch, int hw, uint32_t* ws, uint32_t* pool, int pool_words, int* cursor, l2s_rle_span* span,
+                                             uint32_t* wsum, int* wmax) {
   RleWs W(ws, nch);
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   uint32_t carry_s = 0; int carry_m = -1;                 // the same in every thread
@@ -89,7 +94,7 @@ __global__ __launch_bounds__(RLE_SCAN_T) void rle_scan_kernel(long nch, int hw, 
     carry_s = ts; carry_m = tm;
     __syncthreads();
   }
-  if (t != 0) return;
+  if (t != 0) return;                                     // (no barrier follows in this function)
   const long n = (long)carry_s + 1;                       // transitions + the closing run
   const long off = *cursor;
   const bool fits = off >= 0 && off + n <= (long)pool_words;
@@ -103,9 +108,30 @@ __global__ __launch_bounds__(RLE_SCAN_T) void rle_scan_kernel(long nch, int hw, 
   }
 }
 
-__global__ __launch_bounds__(256) void rle_write_kernel(int h, int w, int nseg, const uint32_t* ws, uint32_t* pool) {
+__global__ __launch_bounds__(RLE_SCAN_T) void rle_scan_kernel(long nch, int hw, uint32_t* ws, uint32_t* pool, int pool_words, int* cursor,
+                                                              l2s_rle_span* span) {
+  __shared__ uint32_t wsum[RLE_SCAN_T / 64];
+  __shared__ int wmax[RLE_SCAN_T / 64];
+  rle_scan_one(nch, hw, ws, pool, pool_words, cursor, span, wsum, wmax);
+}
+
+// the masks in order: the pool decision is sequential (a mask either fits behind its predecessors or leaves the cursor alone).  Thread 0
+// alone reads and bumps the cursor, so it sees its own earlier writes.
+__global__ __launch_bounds__(RLE_SCAN_T) void rle_scan_batch_kernel(int n, const int* n_valid, long nch, int hw, uint32_t* ws, long ws_stride,
+                                                                    uint32_t* pool, int pool_words, int* cursor, l2s_rle_span* spans) {
+  __shared__ uint32_t wsum[RLE_SCAN_T / 64];
+  __shared__ int wmax[RLE_SCAN_T / 64];
+  int nv = *n_valid;
+  nv = nv < 0 ? 0 : (nv > n ? n : nv);
+  for (int b = 0; b < nv; ++b) rle_scan_one(nch, hw, ws + (long)b * ws_stride, pool, pool_words, cursor, spans + b, wsum, wmax);
+  for (int b = nv + threadIdx.x; b < n; b += RLE_SCAN_T) { spans[b].off = 0; spans[b].n = 0; }
+}
+
+__global__ __launch_bounds__(256) void rle_write_kernel(int h, int w, int nseg, const uint32_t* ws, long ws_stride, const int* n_valid, uint32_t* pool) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, seg = blockIdx.y;
   if (x >= w) return;
+  if (n_valid && (int)blockIdx.z >= *n_valid) return;
+  ws += (long)blockIdx.z * ws_stride;
   const long nch = (long)w * nseg, c = (long)x * nseg + seg;
   const RleWs W((uint32_t*)ws, nch);
   if (!W.hdr[0]) return;                                  // the pool is too small: nothing is written
@@ -137,9 +163,23 @@ extern "C" int l2s_rle_from_mask(const uint8_t* mask, int h, int w, uint32_t* po
   const int nseg = cdiv(h, RLE_SEG);
   const long nch = (long)w * nseg;
   const dim3 grid(cdiv(w, 256), nseg);
-  L2S_LAUNCH(rle_count_kernel, grid, dim3(256), 0, s, mask, h, w, nseg, ws);
+  L2S_LAUNCH(rle_count_kernel, grid, dim3(256), 0, s, mask, h, w, nseg, ws, 0L, (const int*)nullptr);
   L2S_LAUNCH(rle_scan_kernel, dim3(1), dim3(RLE_SCAN_T), 0, s, nch, h * w, ws, pool, pool_words, cursor, span);
-  L2S_LAUNCH(rle_write_kernel, grid, dim3(256), 0, s, h, w, nseg, (const uint32_t*)ws, pool);
+  L2S_LAUNCH(rle_write_kernel, grid, dim3(256), 0, s, h, w, nseg, (const uint32_t*)ws, 0L, (const int*)nullptr, pool);
+  return l2s_check_launch();
+}
+
+extern "C" int l2s_rle_from_masks(const uint8_t* masks, int n, const int* n_valid, int h, int w, uint32_t* pool, int pool_words, int* cursor,
+                                  l2s_rle_span* spans, uint32_t* ws, hipStream_t s) {
+  if (!masks || !n_valid || !pool || !cursor || !spans || !ws || n <= 0 || n > 65535 || h <= 0 || w <= 0 || pool_words < 0 ||
+      (long)h * w >= (1L << 31))
+    return L2S_EINVAL;
+  const int nseg = cdiv(h, RLE_SEG);
+  const long nch = (long)w * nseg, stride = l2s_rle_encode_ws_words(h, w);
+  const dim3 grid(cdiv(w, 256), nseg, n);
+  L2S_LAUNCH(rle_count_kernel, grid, dim3(256), 0, s, masks, h, w, nseg, ws, stride, n_valid);
+  L2S_LAUNCH(rle_scan_batch_kernel, dim3(1), dim3(RLE_SCAN_T), 0, s, n, n_valid, nch, h * w, ws, stride, pool, pool_words, cursor, spans);
+  L2S_LAUNCH(rle_write_kernel, grid, dim3(256), 0, s, h, w, nseg, (const uint32_t*)ws, stride, n_valid, pool);
   return l2s_check_launch();
 }
 

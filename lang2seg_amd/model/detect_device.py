@@ -1,0 +1,182 @@
+"""Every instance per sentence: the reference's full Mask R-CNN test path (pyutils/mask-faster-rcnn/lib/model/test.py:268-297,310-344)
+on the device, next to the one-box pick of model/eval_device.py.  Per sentence, behind Network.forward_test_sentence:
+    l2s_detect_nms      per class: score > thresh, order, greedy NMS with cfg.TEST.NMS (one workgroup per class)
+    l2s_detect_select   max_per_image over all classes, the detections in class order, the mask head's RoIs and labels
+    the n-row mask head on `cap` rows, each with its own class (networks with a mask branch)
+    l2s_detect_paste    recover_masks + > 122 of every kept detection into its canvas, the areas
+    l2s_rle_from_masks  the canvases as COCO run lengths in the image's pool (three launches)
+No host synchronisation per sentence; one read-back per image (the records, counts and spans, then the used part of the pool).  Nothing
+is dropped: a sentence with more detections than `cap`, or whose run lengths overflowed the pool, runs again with buffers sized from the
+counts its first run reported (the backbone map of forward_test_image is still there)."""
+import numpy as np
+import torch
+
+from .. import ops as O
+from . import eval_device as ED
+from .config import cfg
+
+_REC = O.DET_RECORD_BYTES // 4                                 # int32 words of one record
+
+
+def default_cap(max_per_image):
+    """rows of the detection buffers: max_per_image rounded up to a multiple of 64, 512 without a limit (a guess, not a bound)"""
+    return (int(max_per_image) + 63) // 64 * 64 if max_per_image > 0 else 512
+
+
+def _pool_budget(cap, iw):
+    """run-length words for `cap` masks: eval_device._Export's per-mask budget"""
+    return cap * (iw * (int(cfg.MASK_SIZE) + 2) + 2)
+
+
+def detect_sentence(net, s, scale, ih, iw, max_per_image, thresh, cap, rec=None, count=None, spans=None, pool=None, cursor=None,
+                    boxes_dump=None):
+    """s: the dict of Network.forward_test_sentence.  -> dict of device buffers: rec int32 [cap][8] (l2s_det_record), count int32 [2]
+    (written, total), and with a mask branch mask_prob f32 [cap][MS][MS] (the net's buffer: valid until its next mask head pass),
+    canvases uint8 [cap][ih][iw], spans int32 [cap][2], pool, cursor.  rec, count, spans, pool, cursor: the caller's (an image's pool
+    shared by its sentences), allocated here when None.  The mask head reuses the heads' buffers: read s's outputs before this call.
+    No host synchronisation."""
+    dev = torch.device(net.device)
+    C, post = net._num_classes, s['post']
+    with_masks = getattr(net, 'variant', None) != 'vgg'
+    i32 = torch.int32
+    rec = torch.empty((cap, _REC), dtype=i32, device=dev) if rec is None else rec
+    count = torch.empty((2,), dtype=i32, device=dev) if count is None else count
+    ws = net.buf('det.ws', ((O.detect_ws_bytes(post, C) + 3) // 4,), i32)
+    roi = net.buf('det.mask_rois', (cap, 5), torch.float32)
+    lab = net.buf('det.mask_labels', (cap,), i32)
+    O.detect_nms(s['cls_prob'], s['bbox_pred'], s['rois'], s['nkeep'], post, C, scale, ih, iw, cfg.TEST.BBOX_REG, thresh, float(cfg.TEST.NMS),
+                 ws, boxes_dump)
+    O.detect_select(ws, post, C, max_per_image, scale, rec, roi, lab, cap, count)
+    out = dict(rec=rec, count=count)
+    if not with_masks:
+        return out
+    MS = int(cfg.MASK_SIZE)
+    Hc, Wc = s['net_conv_hw']
+    mprob = net._roi_heads_test(s['net_conv'], Hc, Wc, roi, cap, labels=lab)[3].view(cap, MS, MS)
+    canvases = net.buf('det.canvases', (cap, ih, iw), torch.uint8)
+    O.detect_paste(mprob, rec, count, ih, iw, canvases)
+    spans = torch.empty((cap, 2), dtype=i32, device=dev) if spans is None else spans
+    if pool is None:
+        pool = torch.empty((_pool_budget(cap, iw),), dtype=i32, device=dev)
+        cursor = torch.zeros((1,), dtype=i32, device=dev)
+    rws = net.buf('det.rle_ws', (cap * O.rle_encode_ws_words(ih, iw),), i32)
+    O.rle_from_masks(canvases, count[0:1], pool, cursor, spans, rws)
+    out.update(mask_prob=mprob, canvases=canvases, spans=spans, pool=pool, cursor=cursor)
+    return out
+
+
+class _Detector(object):
+    """the device side of one image's detections: per sentence `cap` records, the count and the spans in one int32 array (one read-back),
+    the image's run-length pool"""
+
+    def __init__(self, net, S, scale, ih, iw, max_per_image, thresh, cap=None, pool_words=None, capture=None):
+        self.net, self.S, self.scale, self.ih, self.iw = net, S, scale, ih, iw
+        self.max_per_image, self.thresh = int(max_per_image), float(thresh)
+        self.cap = cap = default_cap(max_per_image) if cap is None else int(cap)
+        self.with_masks = getattr(net, 'variant', None) != 'vgg'
+        self.capture = capture
+        dev = torch.device(net.device)
+        # meta: the pool cursor; per sentence (written, total), cap records, cap spans
+        self.stride = 2 + cap * (_REC + 2)
+        self.meta = torch.zeros((1 + S * self.stride,), dtype=torch.int32, device=dev)
+        if self.with_masks:
+            words = S * _pool_budget(cap, iw) if pool_words is None else int(pool_words)
+            self.pool = torch.empty((max(words, 1),), dtype=torch.int32, device=dev)
+
+    def _views(self, meta, i):
+        b = 1 + i * self.stride
+        cap = self.cap
+        return meta[b:b + 2], meta[b + 2:b + 2 + cap * _REC].reshape(cap, _REC), meta[b + 2 + cap * _REC:b + self.stride].reshape(cap, 2)
+
+    def run(self, i, s):
+        """sentence i of the image on the outputs `s` of its forward_test_sentence"""
+        count, rec, spans = self._views(self.meta, i)
+        cap_in = None
+        if self.capture is not None:                              # checks: the heads' outputs before the mask head reuses their buffers
+            cap_in = dict(cls_prob=s['cls_prob'].clone(), bbox_pred=s['bbox_pred'].clone(), rois=s['rois'].clone(),
+                          nkeep=None if s['nkeep'] is None else s['nkeep'].clone(), post=s['post'])
+        out = detect_sentence(self.net, s, self.scale, self.ih, self.iw, self.max_per_image, self.thresh, self.cap, rec=rec, count=count,
+                              spans=spans, pool=self.pool if self.with_masks else None, cursor=self.meta[0:1])
+        if cap_in is not None:
+            if self.with_masks:
+                cap_in['mask_prob'] = out['mask_prob'].clone()
+            self.capture.append(cap_in)
+
+    def collect(self, file_name, resentence, extra=None):
+        """the read-back -> one list of dicts per sentence.  resentence(i): forward_test_sentence of sentence i again (a sentence that did
+        not fit its buffers runs again with the sizes its counts ask for)."""
+        meta = self.meta.cpu().numpy()
+        pool = self.pool[:int(meta[0])].cpu().numpy().view('<u4') if self.with_masks else None
+        out = []
+        for i in range(self.S):
+            count, rec, spans = self._views(meta, i)
+            written, total = int(count[0]), int(count[1])
+            fits = total <= self.cap and not (self.with_masks and (spans[:written, 0] < 0).any())
+            if fits:
+                out.append(self._dicts(rec[:written], spans[:written], pool, file_name, i, extra))
+                continue
+            if self.capture is not None:
+                self.capture.append(dict(rerun=i))
+            cap = max(total, 1)
+            words = int(spans[:written, 1].astype(np.int64).sum()) if total <= self.cap else _pool_budget(cap, self.iw)
+            while True:                                            # sizes grow with every round: the counts of `total` masks are a finite sum
+                one = _Detector(self.net, 1, self.scale, self.ih, self.iw, self.max_per_image, self.thresh, cap=cap, pool_words=words)
+                one.run(0, resentence(i))
+                m1 = one.meta.cpu().numpy()
+                c1, r1, s1 = one._views(m1, 0)
+                if int(c1[1]) > cap:
+                    raise RuntimeError('detection: %d detections in the second run of a sentence, %d in its first' % (int(c1[1]), cap))
+                if self.with_masks and (s1[:int(c1[0]), 0] < 0).any():
+                    words = int(s1[:int(c1[0]), 1].astype(np.int64).sum())
+                    continue
+                p1 = one.pool[:int(m1[0])].cpu().numpy().view('<u4') if self.with_masks else None
+                out.append(self._dicts(r1[:int(c1[0])], s1[:int(c1[0])], p1, file_name, i, extra))
+                break
+        return out
+
+    def _dicts(self, rec, spans, pool, file_name, i, extra):
+        roi, cls, box, score, area = O.det_record_fields(np.ascontiguousarray(rec))
+        res = []
+        for k in range(rec.shape[0]):
+            p = dict(file_name=file_name, sent_index=i, roi=int(roi[k]), category_id=int(cls[k]), box=[float(v) for v in box[k]],
+                     score=float(score[k]))
+            if extra:
+                p.update(extra)
+            if self.with_masks:
+                off, n = int(spans[k, 0]), int(spans[k, 1])
+                p['area'] = int(area[k])
+                p['segmentation'] = dict(size=[self.ih, self.iw], counts=O.rle_to_string(pool[off:off + n]))
+            res.append(p)
+        return res
+
+
+def detect_image(net, data, labels, max_per_image=100, thresh=0.0, _cap=None, _pool_words=None, _capture=None):
+    """data: {'data': float32 (1, H, W, 3) blob, 'im_info': [H, W, scale]} (+ 'file_name'); labels: int [S][T] token ids, zero padded.
+    -> one list per sentence of dicts, class ascending and inside a class score descending: file_name, sent_index, roi (the proposal's
+    row), category_id, box [x1, y1, x2, y2] (original image), score and (networks with a mask branch) area and segmentation
+    {'size': [ih, iw], 'counts': COCO RLE string}.  max_per_image <= 0: no limit; ties at the limit all stay.
+    (_cap, _pool_words: the buffers' first sizes instead of the defaults; _capture: a list that receives each sentence's head outputs and
+    mask probabilities as device copies - checks.)"""
+    labels = np.asarray(labels)
+    if labels.ndim != 2 or labels.shape[0] < 1:
+        raise ValueError('labels: an int array [S][T] with S >= 1, got shape %s' % (labels.shape,))
+    if ((labels != 0).sum(1) == 0).any():
+        raise ValueError('labels: every sentence needs at least one token')
+    S = int(labels.shape[0])
+    d = dict(data=data['data'], im_info=data['im_info'], labels=labels.astype(np.int64),
+             gt_boxes=np.zeros((S, 5), np.float32), gt_masks=np.zeros((S, 1, 1), np.uint8))
+    net.eval()
+    img, lab_d, lens, _, _ = ED._upload_image(net, d, S)
+    im_info = np.asarray(data['im_info'], dtype=np.float32).reshape(-1)[:3]
+    scale, ih, iw = ED._geometry(im_info)
+    dd = dict(data=img, im_info=im_info, S=1)
+    net.forward_test_image(dd)
+    det = _Detector(net, S, scale, ih, iw, max_per_image, thresh, _cap, _pool_words, _capture)
+
+    def sentence(i):
+        dd['labels'] = lab_d[i, :lens[i]]
+        dd['T'] = lens[i]
+        return net.forward_test_sentence(dd)
+    for i in range(S):
+        det.run(i, sentence(i))
+    return det.collect(data.get('file_name'), sentence)

@@ -131,9 +131,11 @@ class _Export(object):
         return out
 
 
-def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1):
+def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1, detect=None):
     """every sentence of one image through the device path; record base + i for sentence i.  No host synchronisation.
-    pool_words >= 0 or None: also keep the predictions on the device (None: the default pool budget) -> the image's _Export"""
+    pool_words >= 0 or None: also keep the predictions on the device (None: the default pool budget) -> the image's _Export.
+    detect: None, or a dict (max_per_image, thresh) that asks for every detection of each sentence too (model/detect_device.py) and
+    receives 'detector' (the image's _Detector) and 'sentence' (forward_test_sentence of sentence i again, for its re-runs)"""
     img, lab_d, lens, box_d, gm = _upload_image(net, data, n_sent)
     im_info = np.asarray(data['im_info'], dtype=np.float32).reshape(-1)[:3]
     scale, ih, iw = _geometry(im_info)
@@ -143,10 +145,18 @@ def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1):
     roi = net.buf('eval.mask_roi', (1, 5), torch.float32)
     lab = net.buf('eval.mask_label', (1,), torch.int32)
     ex = None if pool_words == -1 else _Export(torch.device(net.device), n_sent, ih, iw, with_masks, pool_words)
-    for i in range(n_sent):
+
+    def sentence(i):
         d['labels'] = lab_d[i, :lens[i]]
         d['T'] = lens[i]
-        s = net.forward_test_sentence(d)
+        return net.forward_test_sentence(d)
+    det = None
+    if detect is not None:
+        from .detect_device import _Detector
+        det = detect['detector'] = _Detector(net, n_sent, scale, ih, iw, detect.get('max_per_image', 100), detect.get('thresh', 0.0))
+        detect['sentence'] = sentence
+    for i in range(n_sent):
+        s = sentence(i)
         O.eval_pick(s['cls_prob'], s['bbox_pred'], s['rois'], s['nkeep'], s['post'], net._num_classes, scale, ih, iw, box_d[i],
                     cfg.TEST.BBOX_REG, rec, base + i, roi, lab)
         if ex is not None:
@@ -157,6 +167,8 @@ def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1):
             O.eval_mask_iou(mprob, rec, base + i, gm[i], ih, iw, canvas=None if ex is None else ex.canvas[i])
             if ex is not None:
                 ex.encode(i)
+        if det is not None:                                   # last: its mask head pass reuses the heads' buffers
+            det.run(i, s)
     return ex
 
 
@@ -188,7 +200,7 @@ class _Totals(object):
                 details.append((int(roi[j]), int(cls[j]), box[j].copy(), int(hit[j]), int(Is[j]), int(Us[j])))
 
 
-def _run(loader, model, split, opt, rank, world, details, with_masks, progress, predictions=None, pool_words=None):
+def _run(loader, model, split, opt, rank, world, details, with_masks, progress, predictions=None, pool_words=None, detections=None):
     num_sents = opt.get('num_sents', -1)
     verbose = opt.get('verbose', True)
     if world > 1 and num_sents > 0:
@@ -210,13 +222,21 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
             if num_sents > 0:
                 n = min(n, num_sents - issued)
             rec = O.eval_records(n, device)
-            ex = _eval_image(model, data, n, rec, 0, with_masks, -1 if predictions is None else pool_words)
+            dopt = None if detections is None else dict(max_per_image=opt.get('max_per_image', 100), thresh=opt.get('det_thresh', 0.0))
+            if dopt is None:
+                ex = _eval_image(model, data, n, rec, 0, with_masks, -1 if predictions is None else pool_words)
+            else:
+                ex = _eval_image(model, data, n, rec, 0, with_masks, -1 if predictions is None else pool_words, detect=dopt)
             chunks.append(rec)
             issued += n
             if ex is not None:                                 # one read-back per image: records, spans and cursor, then the pool's used part
                 rec_h = rec.cpu()
                 predictions.extend(ex.collect(rec_h, data.get('file_name')))
                 chunks[-1] = rec_h
+            if dopt is not None:                               # one read-back per image; a sentence that did not fit its buffers runs again
+                extra = dict(image_id=data['image_id']) if 'image_id' in data else None
+                for lst in dopt['detector'].collect(data.get('file_name'), dopt['sentence'], extra):
+                    detections.extend(lst)
             if verbose:                                        # one host synchronisation per image, for the progress line
                 for r in chunks:
                     tot.add(r.cpu(), details, with_masks)
@@ -240,25 +260,27 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
     return tot
 
 
-def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=None, predictions=None, _pool_words=None):
+def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=None, predictions=None, _pool_words=None, detections=None):
     """model/test.py eval_split on the device.  Returns its 7-tuple (acc, eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U,
     num_sent).  details: a list that receives (pred_roi, pred_class, pred_box, hit, I, U) per sentence of this rank.
     predictions: a list that receives one dict per sentence of this rank: file_name, sent_index (position in the image's test batch),
     category_id, box [x1, y1, x2, y2] (original image), score, hit, I, U and segmentation {'size': [ih, iw], 'counts': COCO RLE string}.
+    detections: a list that receives every detection of every sentence of this rank (model/detect_device.py detect_image's dicts, flat;
+    opt['max_per_image'] (100) and opt['det_thresh'] (0.0) are its limits).  Metrics and predictions do not depend on it.
     (_pool_words: the run-length pool of an image in words instead of its default budget; checks of the host fallback.)"""
     def progress(data, t):
         b = data['bounds']
         print('evaluating [%s] ... image[%d/%d]\'s sents, det acc=%.2f%%, seg acc=%.2f%%, seg IoU=%.2f%%' % (
             split, b['it_pos_now'], b['it_max'], t.acc * 100.0 / max(t.loss_evals, 1), t.seg_correct[0] * 100.0 / max(t.seg_total, 1),
             t.cum_I * 100.0 / max(t.cum_U, 1)))
-    t = _run(loader, model, split, opt, rank, world, details, True, progress, predictions, _pool_words)
+    t = _run(loader, model, split, opt, rank, world, details, True, progress, predictions, _pool_words, detections)
     return t.acc / t.loss_evals, EVAL_SEG_IOU_LIST, t.seg_correct, t.seg_total, t.cum_I, t.cum_U, t.num_sent
 
 
-def eval_split_vgg_device(loader, model, crit, split, opt, rank=0, world=1, details=None, predictions=None):
+def eval_split_vgg_device(loader, model, crit, split, opt, rank=0, world=1, details=None, predictions=None, detections=None):
     """model/test_vgg.py eval_split on the device (boxes only: the VGG16 network has no mask branch) -> (acc, num_sent).
-    predictions: as in eval_split_device, without I, U's mask meaning and without `segmentation`"""
+    predictions: as in eval_split_device, without I, U's mask meaning and without `segmentation`; detections: as there, boxes only"""
     def progress(data, t):
         print('evaluating [%s] ... sent %d, det acc=%.2f%%' % (split, t.loss_evals, t.acc * 100.0 / max(t.loss_evals, 1)))
-    t = _run(loader, model, split, opt, rank, world, details, False, progress, predictions)
+    t = _run(loader, model, split, opt, rank, world, details, False, progress, predictions, detections=detections)
     return t.acc * 1.0 / max(t.loss_evals, 1), t.loss_evals

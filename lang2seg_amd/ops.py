@@ -588,6 +588,58 @@ def eval_mask_iou(mask_prob, rec, i, gt, ih, iw, canvas=None):
          ptr(canvas), stream())
 
 
+def rle_from_masks(masks, n_valid, pool, cursor, spans, ws):
+    """rle_from_mask for masks uint8 [n][h][w] in three launches: the first *n_valid (device int32 [1]) masks in order, spans int32 [n][2]
+    (skipped masks: (0, 0)); ws: n * rle_encode_ws_words(h, w) uint32.  No host sync."""
+    n, h, w = masks.shape
+    if ws.numel() < n * rle_encode_ws_words(h, w) or spans.numel() < 2 * n:
+        raise ValueError('rle_from_masks: workspace of %d words, %d needed (spans %d of %d)' % (ws.numel(), n * rle_encode_ws_words(h, w), spans.numel(), 2 * n))
+    call('l2s_rle_from_masks', ptr(masks), n, ptr(n_valid), h, w, ptr(pool), pool.numel(), ptr(cursor), ptr(spans), ptr(ws), stream())
+
+
+DET_RECORD_BYTES = 32      # l2s_det_record: roi, cls (int32), box[4], score (f32), area (int32)
+
+
+def det_record_fields(rec):
+    """host int32 [n][8] detection records -> (roi, cls, box [n][4] f32, score f32, area) numpy arrays"""
+    a = rec.numpy() if isinstance(rec, torch.Tensor) else rec
+    a = a.reshape(-1, DET_RECORD_BYTES // 4)
+    return a[:, 0], a[:, 1], a[:, 2:6].view('<f4'), a[:, 6].view('<f4'), a[:, 7]
+
+
+def detect_ws_bytes(post, ncls):
+    return int(_lib.load().l2s_detect_ws_bytes(int(post), int(ncls)))
+
+
+def detect_nms(cls_prob, bbox_pred, rois, nkeep, post, ncls, im_scale, im_h, im_w, bbox_reg, thresh, nms_thresh, ws, boxes_dump=None):
+    """class-wise NMS of one sentence's head outputs (one workgroup per class) -> the kept lists in ws (detect_ws_bytes(post, ncls) bytes);
+    boxes_dump: optional float32 [post][ncls][4], every decoded box"""
+    if ws.numel() * ws.element_size() < detect_ws_bytes(post, ncls):
+        raise ValueError('detect_nms: workspace of %d bytes, %d needed' % (ws.numel() * ws.element_size(), detect_ws_bytes(post, ncls)))
+    if boxes_dump is not None and boxes_dump.numel() < post * ncls * 4:
+        raise ValueError('detect_nms: boxes_dump of %d floats, %d needed' % (boxes_dump.numel(), post * ncls * 4))
+    call('l2s_detect_nms', ptr(cls_prob), ptr(bbox_pred), ptr(rois), ptr(nkeep), post, ncls, float(im_scale), im_h, im_w, 1 if bbox_reg else 0,
+         float(thresh), float(nms_thresh), ptr(ws), ptr(boxes_dump), stream())
+
+
+def detect_select(ws, post, ncls, max_per_image, im_scale, rec, mask_rois, mask_labels, cap, count):
+    """the top-N rule over all classes and the compaction in class order: rec int32 [cap][8], mask_rois f32 [cap][5], mask_labels int32 [cap],
+    count int32 [2] = (written, total)"""
+    if rec.numel() * rec.element_size() < cap * DET_RECORD_BYTES or mask_rois.numel() < 5 * cap or mask_labels.numel() < cap or count.numel() < 2:
+        raise ValueError('detect_select: an output is smaller than cap = %d rows' % cap)
+    call('l2s_detect_select', ptr(ws), post, ncls, int(max_per_image), float(im_scale), ptr(rec), ptr(mask_rois), ptr(mask_labels), cap, ptr(count),
+         stream())
+
+
+def detect_paste(mask_prob, rec, count, ih, iw, canvases):
+    """recover_masks + > 122 of mask_prob f32 [cap][ms][ms] on the records' boxes -> canvases uint8 [cap][ih][iw], areas added to the records;
+    only the first count[0] detections"""
+    cap, ms = mask_prob.shape[0], mask_prob.shape[-1]
+    if canvases.numel() < cap * ih * iw or rec.numel() * rec.element_size() < cap * DET_RECORD_BYTES:
+        raise ValueError('detect_paste: canvases or records smaller than cap = %d' % cap)
+    call('l2s_detect_paste', ptr(mask_prob), ms, ptr(rec), ptr(count), cap, ih, iw, ptr(canvases), stream())
+
+
 def rcnn_predict(heads, ldh, R, ncls, stds4, means4, cls_prob, bbox_pred):
     call('l2s_rcnn_predict', ptr(heads), ldh, R, ncls, ptr(stds4), ptr(means4), ptr(cls_prob), ptr(bbox_pred), stream())
 

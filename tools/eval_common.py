@@ -28,18 +28,22 @@ def parse_args(argv=None):
                    'sharded over RANK / WORLD_SIZE); 0: the host loop model/test.py')
     p.add_argument('--dump_predictions', default=None, help='with --device_eval 1: write every sentence\'s prediction (class, box, score, hit, '
                    'I, U, COCO RLE mask) as one JSON list to this path (rank r of WORLD_SIZE > 1 writes PATH.rank<r>)')
+    p.add_argument('--dump_detections', default=None, help='with --device_eval 1: write every detection of every sentence (class-wise NMS with '
+                   'cfg.TEST.NMS, --max_per_image, --det_thresh; box, score, area, COCO RLE mask) as one JSON list to this path (rank suffix as above)')
+    p.add_argument('--max_per_image', type=int, default=100, help='--dump_detections: detections kept per sentence over all classes (<= 0: all)')
+    p.add_argument('--det_thresh', type=float, default=0.0, help='--dump_detections: a detection needs a score above this')
     return vars(p.parse_args(argv))
 
 
-def dump_predictions(args, preds, rank, world):
-    """--dump_predictions: this rank's predictions as one JSON list"""
+def dump_predictions(args, preds, rank, world, key='dump_predictions', what='predictions'):
+    """--dump_predictions / --dump_detections: this rank's list as one JSON list"""
     if preds is None:
         return
     import json
-    path = args['dump_predictions'] + ('.rank%d' % rank if world > 1 else '')
+    path = args[key] + ('.rank%d' % rank if world > 1 else '')
     with open(path, 'w') as f:
         json.dump(preds, f)
-    print('wrote %d predictions to %s' % (len(preds), path))
+    print('wrote %d %s to %s' % (len(preds), what, path))
 
 
 def main(args, variant):
@@ -54,7 +58,10 @@ def main(args, variant):
         raise ValueError('WORLD_SIZE > 1 evaluates through --device_eval 1 only')
     if args.get('dump_predictions') and not args['device_eval']:
         raise ValueError('--dump_predictions needs --device_eval 1 (the host loop keeps no predictions)')
+    if args.get('dump_detections') and not args['device_eval']:
+        raise ValueError('--dump_detections needs --device_eval 1 (the host loop keeps one box per sentence)')
     preds = [] if args.get('dump_predictions') else None
+    dets = [] if args.get('dump_detections') else None
     torch.cuda.set_device(local % max(torch.cuda.device_count(), 1))
     T = 20 if args['dataset'] == 'refcocog' else 10
     V = 3349 if args['dataset'] == 'refcocog' else 1999
@@ -96,11 +103,13 @@ def main(args, variant):
     split = args['split'] if args['split'] in loader.split_ix else 'val'
     if variant == 'vgg':                                     # tools/eval_vgg.py: boxes only (model/test_vgg.py)
         from lang2seg_amd.model.test_vgg import eval_split as eval_split_vgg
-        eopt = dict(num_sents=args['num_sents'], verbose=bool(args['verbose']))
+        eopt = dict(num_sents=args['num_sents'], verbose=bool(args['verbose']), max_per_image=args.get('max_per_image', 100),
+                    det_thresh=args.get('det_thresh', 0.0))
         if args['device_eval']:
             from lang2seg_amd.model.eval_device import eval_split_vgg_device
-            acc, n = eval_split_vgg_device(loader, net, None, split, eopt, rank=rank, world=world, predictions=preds)
+            acc, n = eval_split_vgg_device(loader, net, None, split, eopt, rank=rank, world=world, predictions=preds, detections=dets)
             dump_predictions(args, preds, rank, world)
+            dump_predictions(args, dets, rank, world, 'dump_detections', 'detections')
         else:
             acc, n = eval_split_vgg(loader, net, None, split, eopt)
         if rank != 0:
@@ -108,11 +117,13 @@ def main(args, variant):
         print('Comprehension on %s\'s %s (%s sents): box acc %.2f%%' % (opt['dataset_splitBy'], args['split'], n, acc * 100))
         return acc, None, None
     opt['split'], opt['id'] = args['split'], args['id']
-    eopt = dict(num_sents=args['num_sents'], verbose=bool(args['verbose']))
+    eopt = dict(num_sents=args['num_sents'], verbose=bool(args['verbose']), max_per_image=args.get('max_per_image', 100),
+                det_thresh=args.get('det_thresh', 0.0))
     if args['device_eval']:
         from lang2seg_amd.model.eval_device import eval_split_device
-        res = eval_split_device(loader, net, None, split, eopt, rank=rank, world=world, predictions=preds)
+        res = eval_split_device(loader, net, None, split, eopt, rank=rank, world=world, predictions=preds, detections=dets)
         dump_predictions(args, preds, rank, world)
+        dump_predictions(args, dets, rank, world, 'dump_detections', 'detections')
     else:
         res = eval_split(loader, net, None, split, eopt)
     acc, eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U, num_sent = res

@@ -3,7 +3,10 @@
     python tools/predict.py --image FILE --sent "the man on the left" --sent "red umbrella" [--png DIR]
     python tools/predict.py --synthetic 1 --allow_init_weights 1                       (a SyntheticLoader image and its token ids)
 Prints one JSON list: per sentence the class, the box, the score, the mask's area and its COCO run-length form.  --png DIR also writes
-each mask as DIR/<image>_<sent_index>.png, decoded on the device from the run lengths (l2s_rle_to_mask): the round trip."""
+each mask as DIR/<image>_<sent_index>.png, decoded on the device from the run lengths (l2s_rle_to_mask): the round trip.
+    --all_detections 1 [--max_per_image N] [--det_thresh T]: every instance the network finds for each sentence instead of its first
+pick (model/detect_device.py: class-wise NMS with cfg.TEST.NMS, the best N over all classes); prints one list per sentence, --png writes
+DIR/<image>_<sent_index>_<k>.png."""
 import argparse
 import json
 import os
@@ -26,6 +29,8 @@ def parse_args(argv=None):
     p.add_argument('--output_postfix', default='cycle'); p.add_argument('--model_iter', type=int, default=0)
     p.add_argument('--cfg', dest='cfg_file', default='experiments/cfgs/res101.yml'); p.add_argument('--dtype', default='bf16')
     p.add_argument('--allow_init_weights', type=int, default=0)
+    p.add_argument('--all_detections', type=int, default=0); p.add_argument('--max_per_image', type=int, default=100)
+    p.add_argument('--det_thresh', type=float, default=0.0)
     return vars(p.parse_args(argv))
 
 
@@ -85,6 +90,17 @@ def main(args):
         net.load_state_dict(torch.load(ckpt, map_location='cpu'))
     elif not args['allow_init_weights']:
         raise FileNotFoundError('no snapshot at %s (--allow_init_weights 1 predicts with the initialisers)' % ckpt)
+    if args.get('all_detections'):
+        from lang2seg_amd.model.detect_device import detect_image
+        dets = detect_image(net, data, labels, max_per_image=args['max_per_image'], thresh=args['det_thresh'])
+        if args['png']:
+            os.makedirs(args['png'], exist_ok=True)
+            for lst in dets:
+                for k, p in enumerate(lst):
+                    if 'segmentation' in p:
+                        write_png(p, osp.join(args['png'], '%s_%d_%d.png' % (osp.splitext(p['file_name'])[0], p['sent_index'], k)))
+        print(json.dumps(dets))
+        return dets
     preds = predict_image(net, data, labels)
     if args['png']:
         os.makedirs(args['png'], exist_ok=True)
