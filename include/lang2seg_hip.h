@@ -354,6 +354,32 @@ int l2s_lstm_step_bwd(const l2s_lstm_bwd_dir* dirs, int ndir, int Hh, hipStream_
 int l2s_lstm_cell_fwd(const float* gates, const float* c_prev, float* c, float* h, float* act /*[4H] saved*/, int Hh, hipStream_t s);
 int l2s_lstm_cell_bwd(const float* dh, const float* dc_in, const float* act, const float* c_prev, const float* c,
                       float* dgates, float* dc_prev, int Hh, hipStream_t s);
+/* Fused GRU time step (nn.GRU, gate rows r,z,n; lang_encoder.py:21-24 with rnn_type 'gru'), one launch for up to two directions.
+ * forward : a = W_hh h_prev + b_hh; r = sigmoid(gi_r + a_r), z = sigmoid(gi_z + a_z), n = tanh(gi_n + r a_n), h = (1 - z) n + z h_prev
+ *           with gates_in[3H] = x W_ih^T + b_ih (precomputed); stores h and act[4H] = r, z, n, a_n
+ * backward: dh = w_hh_T[H][3H] . dgh_next (NULL at the first processed step) + dh_ext (NULL or [H], any step) + dh_carry_in (NULL or [H]);
+ *           dgi[3H] = (da_r, da_z, da_n) is the gradient of gates_in (feeds W_ih, b_ih, dx), dgh[3H] = (da_r, da_z, da_n r) the gradient
+ *           of a (feeds W_hh, b_hh and the next step's product), dh_carry_out[H] = dh z the direct path into h_prev (ping-ponged by the host)
+ * H % 4 != 0 or ndir outside {1, 2}: error code, nothing launched (the same for the l2s_rnn_step_* pair). */
+typedef struct { const float* w_hh; const float* b_hh; const float* gates_in; const float* h_prev; float* h; float* act; } l2s_gru_fwd_dir;
+typedef struct { const float* w_hh_T; const float* dgh_next; const float* dh_ext; const float* dh_carry_in; const float* act;
+                 const float* h_prev; float* dgi; float* dgh; float* dh_carry_out; } l2s_gru_bwd_dir;
+int l2s_gru_step_fwd(const l2s_gru_fwd_dir* dirs, int ndir, int Hh, hipStream_t s);
+int l2s_gru_step_bwd(const l2s_gru_bwd_dir* dirs, int ndir, int Hh, hipStream_t s);
+/* Fused Elman time step (nn.RNN, tanh; rnn_type 'rnn').
+ * forward : h = tanh(gates_in[H] + W_hh h_prev + b_hh); h is its own saved activation
+ * backward: dh = w_hh_T[H][H] . dg_next (NULL at the first processed step) + dh_ext (NULL or [H]); dg[H] = dh (1 - h h) */
+typedef struct { const float* w_hh; const float* b_hh; const float* gates_in; const float* h_prev; float* h; } l2s_rnn_fwd_dir;
+typedef struct { const float* w_hh_T; const float* dg_next; const float* dh_ext; const float* h; float* dg; } l2s_rnn_bwd_dir;
+int l2s_rnn_step_fwd(const l2s_rnn_fwd_dir* dirs, int ndir, int Hh, hipStream_t s);
+int l2s_rnn_step_bwd(const l2s_rnn_bwd_dir* dirs, int ndir, int Hh, hipStream_t s);
+/* Stacked layers (any cell).  forward: out[T][ndir H], row t = [h0[t][:] | h1[t][:]] (* mask[T][ndir H], NULL: none) - the next layer's input;
+ * h0 / h1 are [T][H] (h1 unused when ndir == 1).  backward: d0[t][:] / d1[t][:] = the halves of dx[t][:] (* mask) - the per-step dh_ext of
+ * the layer below; add0 / add1 (NULL or [H]) are added to the row each direction processes last (d0: T - 1, d1: 0): the layer's part of
+ * the gradient of `hidden`. */
+int l2s_rnn_concat_fwd(const float* h0, const float* h1, const float* mask, float* out, int T, int Hh, int ndir, hipStream_t s);
+int l2s_rnn_concat_bwd(const float* dx, const float* mask, const float* add0, const float* add1, float* d0, float* d1, int T, int Hh,
+                       int ndir, hipStream_t s);
 /* dynamic-filter correlation (NET:504-562): filt float [7][C] (tanh'ed), r float [7].
  * y(dtype)[HW][C] = x * resp, resp float [HW], respk float [HW][7] (masked per-filter responses) */
 int l2s_dynfilter_fwd(const void* x, const float* filt, const float* r, void* y, float* resp, float* respk, int H, int W, int C,

@@ -51,6 +51,22 @@ class LstmBwdDir(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('w_hh_T', 'dgates_next', 'dh_ext', 'dc_in', 'act', 'c_prev', 'c', 'dgates', 'dc_prev')]
 
 
+class GruFwdDir(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('w_hh', 'b_hh', 'gates_in', 'h_prev', 'h', 'act')]
+
+
+class GruBwdDir(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('w_hh_T', 'dgh_next', 'dh_ext', 'dh_carry_in', 'act', 'h_prev', 'dgi', 'dgh', 'dh_carry_out')]
+
+
+class RnnFwdDir(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('w_hh', 'b_hh', 'gates_in', 'h_prev', 'h')]
+
+
+class RnnBwdDir(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('w_hh_T', 'dg_next', 'dh_ext', 'h', 'dg')]
+
+
 class Bottleneck64Desc(C.Structure):
     _fields_ = [(n, vp) for n in ('a', 'x', 'w2', 'w3', 'wd', 'w1n', 'b2', 'b3', 'bd', 'b1n', 'y', 'a_next')] + [(n, i32) for n in ('H', 'W', 'Cx')]
 
@@ -166,6 +182,12 @@ SIGS = {
     'l2s_detect_paste': (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp]),
     'l2s_lstm_step_fwd': (i32, [vp, i32, i32, vp]),
     'l2s_lstm_step_bwd': (i32, [vp, i32, i32, vp]),
+    'l2s_gru_step_fwd': (i32, [vp, i32, i32, vp]),
+    'l2s_gru_step_bwd': (i32, [vp, i32, i32, vp]),
+    'l2s_rnn_step_fwd': (i32, [vp, i32, i32, vp]),
+    'l2s_rnn_step_bwd': (i32, [vp, i32, i32, vp]),
+    'l2s_rnn_concat_fwd': (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    'l2s_rnn_concat_bwd': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     'l2s_rcnn_predict': (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     'l2s_mask_prob': (i32, [vp, i32, i32, vp, i32, C.c_long, vp, vp]),
     'l2s_response_loss': (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]),

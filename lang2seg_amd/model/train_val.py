@@ -136,7 +136,12 @@ class SolverWrapper(object):
 
     def from_snapshot(self, sfile, nfile):
         print('Restoring model snapshots from {:s}'.format(sfile))
-        self.load_matched(torch.load(str(sfile), map_location='cpu'))
+        saved = torch.load(str(sfile), map_location='cpu')
+        # (load_matched keeps this network's own values where a shape differs: a snapshot of another encoder - rnn_type, rnn_num_layers,
+        # bidirectional - would resume from initialisers without a word)
+        if hasattr(self.net, 'P'):
+            self.net.P.check_encoder_keys(saved)
+        self.load_matched(saved)
         # data parallel: every rank but 0 has its own sidecar (its shard has its own length, permutation and RNG streams); rank 0's file is the
         # reference-format one.  A snapshot written by a single-process or a smaller run lacks some of them.  Whether to go on is decided
         # TOGETHER, before anything else is exchanged: a rank that raised alone would leave the others waiting in their first collective

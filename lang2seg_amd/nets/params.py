@@ -42,6 +42,40 @@ def from_internal(name, t, ref_shape):
     return t.view(ref_shape).contiguous()
 
 
+RNN_GATES = {'lstm': 4, 'gru': 3, 'rnn': 1}      # rows of weight_ih / weight_hh per hidden unit (torch.nn.LSTM / GRU / RNN)
+
+
+def encoder_config(opt):
+    """(rnn_type, layers, directions, gates per unit) of the expression encoder (ENC:21-24); ValueError names the option it rejects"""
+    typ = str(opt.get('rnn_type', 'lstm')).lower()
+    if typ not in RNN_GATES:
+        raise ValueError("rnn_type %r: the encoder has 'lstm', 'gru' and 'rnn' (tanh) cells" % (opt.get('rnn_type'),))
+    layers = int(opt.get('rnn_num_layers', 1))
+    if layers < 1:
+        raise ValueError('rnn_num_layers %r: at least one layer' % (opt.get('rnn_num_layers'),))
+    if int(opt['rnn_hidden_size']) % 4 or int(opt['rnn_hidden_size']) < 4:
+        raise ValueError('rnn_hidden_size %r: the recurrent kernels need a multiple of 4' % (opt['rnn_hidden_size'],))
+    if int(opt.get('variable_lengths', 1)) <= 0:
+        # ENC:60-82 produces `hidden` only on the packed-sequence path
+        raise ValueError('variable_lengths %r: the reference encoder returns no hidden state with variable_lengths 0' % (opt.get('variable_lengths'),))
+    return typ, layers, (2 if int(opt.get('bidirectional', 1)) > 0 else 1), RNN_GATES[typ]
+
+
+def encoder_rnn_shapes(opt):
+    """torch's own keys and shapes of nn.LSTM / nn.GRU / nn.RNN(word_vec_size, rnn_hidden_size, rnn_num_layers, bidirectional) under
+    'rnn_encoder.rnn.', in torch's order"""
+    typ, layers, ndir, G = encoder_config(opt)
+    WV, Hh = opt['word_vec_size'], opt['rnn_hidden_size']
+    s = {}
+    for k in range(layers):
+        for sfx in ['', '_reverse'][:ndir]:
+            s['rnn_encoder.rnn.weight_ih_l%d%s' % (k, sfx)] = (G * Hh, WV if k == 0 else ndir * Hh)
+            s['rnn_encoder.rnn.weight_hh_l%d%s' % (k, sfx)] = (G * Hh, Hh)
+            s['rnn_encoder.rnn.bias_ih_l%d%s' % (k, sfx)] = (G * Hh,)
+            s['rnn_encoder.rnn.bias_hh_l%d%s' % (k, sfx)] = (G * Hh,)
+    return s
+
+
 class ParamStore(object):
     def __init__(self, opt, num_layers, num_classes, num_anchors, fixed_blocks, device, dt, variant='cycle'):
         from .variants import VARIANTS
@@ -61,11 +95,7 @@ class ParamStore(object):
         V, E, WV, Hh = o['vocab_size'], o['word_embedding_size'], o['word_vec_size'], o['rnn_hidden_size']
         s['rnn_encoder.embedding.weight'] = (V, E)
         s['rnn_encoder.mlp.0.weight'] = (WV, E); s['rnn_encoder.mlp.0.bias'] = (WV,)
-        for sfx in ['', '_reverse']:
-            s['rnn_encoder.rnn.weight_ih_l0' + sfx] = (4 * Hh, WV)
-            s['rnn_encoder.rnn.weight_hh_l0' + sfx] = (4 * Hh, Hh)
-            s['rnn_encoder.rnn.bias_ih_l0' + sfx] = (4 * Hh,)
-            s['rnn_encoder.rnn.bias_hh_l0' + sfx] = (4 * Hh,)
+        s.update(encoder_rnn_shapes(o))
         if self.var['cap'] is not None:
             R, IE, AH = o['rnn_size'], o['input_encoding_size'], o['att_hid_size']
             s['caption_model.embed.0.weight'] = (V + 1, IE)
@@ -317,9 +347,35 @@ class ParamStore(object):
         return buf[o:o + count]
 
     # ---- (de)serialisation --------------------------------------------------
+    def check_encoder_keys(self, sd):
+        """a state dict that holds a recurrent encoder must hold THIS network's: the cell, the depth and the directions are read off its
+        keys and shapes, and a difference is an error naming the option to change (a dict without encoder tensors passes)"""
+        pre = 'rnn_encoder.rnn.'
+        theirs = {k: tuple(sd[k].shape) for k in sd if k.startswith(pre)}
+        mine = {k: tuple(v) for k, v in self.shapes.items() if k.startswith(pre)}
+        if not theirs or theirs == mine:
+            return
+        typ, layers, ndir, G = encoder_config(self.opt)
+        got, bad = {}, []
+        whh = theirs.get(pre + 'weight_hh_l0')
+        if whh is not None and len(whh) == 2:
+            got['rnn_hidden_size'] = whh[1]
+            got['rnn_type'] = {g: n for n, g in RNN_GATES.items()}.get(whh[0] // max(whh[1], 1), '?')
+        got['rnn_num_layers'] = 1 + max([int(k[len(pre):].split('_l')[1].split('_')[0]) for k in theirs] or [0])
+        got['bidirectional'] = int(any(k.endswith('_reverse') for k in theirs))
+        want = dict(rnn_type=typ, rnn_num_layers=layers, bidirectional=int(ndir == 2), rnn_hidden_size=self.opt['rnn_hidden_size'])
+        for f in ('rnn_type', 'rnn_num_layers', 'bidirectional', 'rnn_hidden_size'):
+            if f in got and got[f] != want[f]:
+                bad.append('--%s %s (this network: %s)' % (f, got[f], want[f]))
+        if not bad:
+            diff = sorted(k for k in set(theirs) | set(mine) if theirs.get(k) != mine.get(k))
+            bad.append('rnn_type / rnn_num_layers / bidirectional / word_vec_size: %s is %s there and %s here' % (diff[0], theirs.get(diff[0]), mine.get(diff[0])))
+        raise ValueError('the state dict holds another language encoder; it was trained with ' + ', '.join(bad))
+
     def load_state_dict(self, sd, strict=False):
         """name+shape matched copy (TV:262-281 semantics live in the solver); tolerates missing
         num_batches_tracked and torch-0.3 checkpoints."""
+        self.check_encoder_keys(sd)
         for k, shp in self.shapes.items():
             if k not in sd:
                 if strict:

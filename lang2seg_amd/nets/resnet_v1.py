@@ -13,7 +13,7 @@ from .. import ops as O
 from .._lib import F32, BF16
 from ..model.config import cfg
 from .network import Network, ConvOp, Bottleneck
-from .params import ParamStore
+from .params import ParamStore, encoder_config
 from .variants import solver_cfg
 from . import anchors as ANC
 
@@ -31,7 +31,7 @@ class resnetv1(Network):
         self.var = VARIANTS[self.variant]
         self._num_layers = num_layers
         self.opt = dict(opt)
-        assert self.opt.get('rnn_type', 'lstm') == 'lstm' and self.opt.get('rnn_num_layers', 1) == 1 and self.opt.get('bidirectional', 1) > 0
+        self.enc = encoder_config(self.opt)      # (rnn_type, layers, directions, gate rows per unit); ValueError names a rejected option
         if self.var['cap'] is not None:
             assert self.opt.get('caption_model', 'att2in2') == 'att2in2', 'only the att2in2 captioner is on the hot path'
         self._cap_loss_weight = float(self.opt.get('cap_loss_weight', 0.0)) if self.var['cap'] is not None else 0.0   # RES:253
@@ -129,9 +129,8 @@ class resnetv1(Network):
             if dst is None:
                 self.wT[name] = (e.wb, N, K)
         # only the matrices whose data gradient is taken one row at a time (inside a recurrence); row batches use bwd_x's MFMA path
-        for sfx in ['', '_reverse']:
-            w = 'rnn_encoder.rnn.weight_hh_l0'
-            add(w + sfx, P.view(w + sfx), *P.shapes[w + sfx])
+        for w in self._encoder_hh_keys():
+            add(w, P.view(w), *P.shapes[w])
         capk = ['caption_model.core.h2h.weight', 'caption_model.core.attention.h2att.weight']
         if not (self.cap_projected and self.opt['rnn_size'] <= 1024):
             capk.append('caption_model.core.a2c.weight')     # (the projected-attention recurrence never multiplies by a2c^T row by row)
@@ -188,66 +187,132 @@ class resnetv1(Network):
     # ------------------------------------------------------------------ language encoder (ENC:27-82)
     # hidden/cell states are kept in (T+1)-row arrays with one all-zero row so that "previous state" is always a row of
     # the same array: forward direction h(t) = row t+1, h(t-1) = row t; reverse direction h(t) = row t, previous = row t+1.
+    # self.enc = (rnn_type, layers, directions, gate rows per unit): nn.LSTM / nn.GRU / nn.RNN(tanh), stacked, one or two directions
+    # (ENC:21-24).  Layer k > 0 reads [h_fwd(t) | h_rev(t)] of layer k-1 (x the inter-layer dropout mask in training).
+    _ENC_STEP = {'lstm': (O.lstm_step_fwd, O.lstm_step_bwd), 'gru': (O.gru_step_fwd, O.gru_step_bwd), 'rnn': (O.rnn_step_fwd, O.rnn_step_bwd)}
+
+    def _encoder_hh_keys(self):
+        """every recurrent matrix of the encoder: their data gradients are taken one row at a time, through transposed copies"""
+        typ, L, ndir, G = self.enc
+        return ['rnn_encoder.rnn.weight_hh_l%d%s' % (l, sfx) for l in range(L) for sfx in ['', '_reverse'][:ndir]]
+
+    def _enc_state(self, l, T, bwd=False):
+        """the per-direction weights and persistent buffers of encoder layer l"""
+        P = self.P
+        typ, L, ndir, G = self.enc
+        Hh = self.opt['rnn_hidden_size']
+        st = []
+        for sfx in ['', '_reverse'][:ndir]:
+            key = lambda n, sfx=sfx: 'rnn_encoder.rnn.%s_l%d%s' % (n, l, sfx)
+            b = sfx if l == 0 else '.l%d%s' % (l, sfx)          # buffer names (layer 0 keeps the single-layer names)
+            q = dict(sfx=sfx, key=key, hs=self.buf('enc.hfull' + b, (T + 1, Hh), f32))
+            if typ == 'lstm':
+                q['cs'] = self.buf('enc.cfull' + b, (T + 1, Hh), f32)
+            if typ != 'rnn':
+                q['act'] = self.buf('enc.act' + b, (T, 4 * Hh), f32)
+            if not bwd:
+                q.update(g=self.buf('enc.gates' + b, (T, G * Hh), f32), wih=P.view(key('weight_ih')), bih=P.view(key('bias_ih')),
+                         whh=P.view(key('weight_hh')), bhh=P.view(key('bias_hh')))
+            else:
+                q['dg'] = self.buf('enc.dg' + b, (T, G * Hh), f32)          # gradient of the gate pre-activations (GRU: of gates_in)
+                if typ == 'gru':
+                    q['dgh'] = self.buf('enc.dgh' + b, (T, G * Hh), f32)    # ... of W_hh h_prev + b_hh
+                    q['carry'] = self.buf('enc.dhc' + b, (2, Hh), f32)
+                if typ == 'lstm':
+                    q['dc'] = self.buf('enc.dc' + b, (2, Hh), f32, zero=True)
+                q['wT'] = self.wT[key('weight_hh')][0]
+            st.append(q)
+        return st
+
     def _encoder_fwd(self, d):
         P, T = self.P, d['T']
-        Hh, E = self.opt['rnn_hidden_size'], self.opt['word_embedding_size']
+        typ, L, ndir, G = self.enc
+        Hh, E, WV = self.opt['rnn_hidden_size'], self.opt['word_embedding_size'], self.opt['word_vec_size']
         t = self.t
         emb = self.buf('enc.emb', (T, E), f32)
         t['enc.drop'] = self._drop('word', (T, E), self.opt['word_drop_out'])
         O.embed_fwd(P.view('rnn_encoder.embedding.weight'), d['labels'], t['enc.drop'], emb, T, E, False)
-        x = self.buf('enc.x', (T, Hh), f32)
-        O.linear_fwd(emb, P.view('rnn_encoder.mlp.0.weight'), P.view('rnn_encoder.mlp.0.bias'), x, T, Hh, E, act=1)
-        hidden = self.buf('enc.hidden', (2 * Hh,), f32)
-        st = []
-        for di, sfx in enumerate(['', '_reverse']):
-            g = self.buf('enc.gates' + sfx, (T, 4 * Hh), f32)
-            O.linear_fwd(x, P.view('rnn_encoder.rnn.weight_ih_l0' + sfx), P.view('rnn_encoder.rnn.bias_ih_l0' + sfx), g, T, 4 * Hh, Hh)
-            st.append(dict(g=g, hs=self.buf('enc.hfull' + sfx, (T + 1, Hh), f32), cs=self.buf('enc.cfull' + sfx, (T + 1, Hh), f32),
-                           act=self.buf('enc.act' + sfx, (T, 4 * Hh), f32), whh=P.view('rnn_encoder.rnn.weight_hh_l0' + sfx),
-                           bhh=P.view('rnn_encoder.rnn.bias_hh_l0' + sfx)))
-        # one launch per time step for both directions (h2h GEMV + cell update fused): T launches instead of 4 T
-        for s_ in range(T):
-            dirs = []
-            for di, q in enumerate(st):
-                tt = s_ if di == 0 else T - 1 - s_
-                cur, prev = (tt + 1, tt) if di == 0 else (tt, tt + 1)
-                dirs.append(dict(w_hh=q['whh'], b_hh=q['bhh'], gates_in=q['g'][tt], h_prev=q['hs'][prev], c_prev=q['cs'][prev],
-                                 c=q['cs'][cur], h=q['hs'][cur], act=q['act'][tt], gates_out=q['g'][tt]))
-            O.lstm_step_fwd(dirs, Hh)
-        O.memcpy(hidden[0:Hh], st[0]['hs'][T]); O.memcpy(hidden[Hh:2 * Hh], st[1]['hs'][0])      # ENC:76-80
+        x = self.buf('enc.x', (T, WV), f32)
+        O.linear_fwd(emb, P.view('rnn_encoder.mlp.0.weight'), P.view('rnn_encoder.mlp.0.bias'), x, T, WV, E, act=1)
+        hidden = self.buf('enc.hidden', (L * ndir * Hh,), f32)
+        step = self._ENC_STEP[typ][0]
+        xin, K = x, WV
+        t['enc.in'], t['enc.ldrop'] = [x], []
+        for l in range(L):
+            st = self._enc_state(l, T)
+            for q in st:
+                O.linear_fwd(xin, q['wih'], q['bih'], q['g'], T, G * Hh, K)
+            # one launch per time step for both directions (h2h GEMV + cell update fused): T launches instead of 4 T
+            for s_ in range(T):
+                dirs = []
+                for di, q in enumerate(st):
+                    tt = s_ if di == 0 else T - 1 - s_
+                    cur, prev = (tt + 1, tt) if di == 0 else (tt, tt + 1)
+                    if typ == 'lstm':
+                        dirs.append(dict(w_hh=q['whh'], b_hh=q['bhh'], gates_in=q['g'][tt], h_prev=q['hs'][prev], c_prev=q['cs'][prev],
+                                         c=q['cs'][cur], h=q['hs'][cur], act=q['act'][tt], gates_out=q['g'][tt]))
+                    else:
+                        dirs.append(dict(w_hh=q['whh'], b_hh=q['bhh'], gates_in=q['g'][tt], h_prev=q['hs'][prev], h=q['hs'][cur],
+                                         act=(q['act'][tt] if typ == 'gru' else None)))
+                step(dirs, Hh)
+            for di, q in enumerate(st):                     # ENC:76-80: h_n flattened, index (layer * ndir + dir) * Hh
+                o = (l * ndir + di) * Hh
+                O.memcpy(hidden[o:o + Hh], q['hs'][T] if di == 0 else q['hs'][0])
+            if l + 1 < L:
+                # nn.LSTM/GRU/RNN(dropout=rnn_drop_out): on every layer's output except the last, training mode only
+                m = self._drop('rnn_l%d' % l, (T, ndir * Hh), float(self.opt.get('rnn_drop_out', 0.0)))
+                xin, K = self.buf('enc.in.l%d' % (l + 1), (T, ndir * Hh), f32), ndir * Hh
+                O.rnn_concat_fwd([st[0]['hs'][1:T + 1]] + [q['hs'][0:T] for q in st[1:]], m, xin, T, Hh)
+                t['enc.in'].append(xin); t['enc.ldrop'].append(m)
         t['enc.emb'], t['enc.x'], t['hidden'] = emb, x, hidden
         return hidden
 
     def _encoder_bwd(self, d, dhidden):
         P, T, t = self.P, d['T'], self.t
-        Hh, E = self.opt['rnn_hidden_size'], self.opt['word_embedding_size']
-        dx = self.buf('enc.dx', (T, Hh), f32, zero=True)
-        st = []
-        for di, sfx in enumerate(['', '_reverse']):
-            st.append(dict(hs=self.buf('enc.hfull' + sfx, (T + 1, Hh), f32), cs=self.buf('enc.cfull' + sfx, (T + 1, Hh), f32),
-                           act=self.buf('enc.act' + sfx, (T, 4 * Hh), f32), dg=self.buf('enc.dg' + sfx, (T, 4 * Hh), f32),
-                           dc=self.buf('enc.dc' + sfx, (2, Hh), f32, zero=True), wT=self.wT['rnn_encoder.rnn.weight_hh_l0' + sfx][0], sfx=sfx))
-        # one launch per time step for both directions: dh = W_hh^T dg(next step) fused with this step's cell backward
-        k = 0
-        for s_ in range(T):
-            dirs = []
+        typ, L, ndir, G = self.enc
+        Hh, E, WV = self.opt['rnn_hidden_size'], self.opt['word_embedding_size'], self.opt['word_vec_size']
+        dx = self.buf('enc.dx', (T, WV), f32, zero=True)
+        step = self._ENC_STEP[typ][1]
+        ext = None          # per direction [T][Hh]: d(loss)/d(h(t)) from the layer above (+ this layer's slice of d(hidden) at its last step)
+        for l in reversed(range(L)):
+            st = self._enc_state(l, T, bwd=True)
+            # one launch per time step for both directions: dh = W_hh^T dg(next step) fused with this step's cell backward
+            k = 0
+            for s_ in range(T):
+                dirs = []
+                for di, q in enumerate(st):
+                    tt = T - 1 - s_ if di == 0 else s_
+                    nxt = tt + 1 if di == 0 else tt - 1               # the step processed just before this one
+                    cur, prev = (tt + 1, tt) if di == 0 else (tt, tt + 1)
+                    o = (l * ndir + di) * Hh
+                    dh_ext = ext[di][tt] if ext is not None else (dhidden[o:o + Hh] if s_ == 0 else None)
+                    if typ == 'lstm':
+                        dirs.append(dict(w_hh_T=q['wT'], dgates_next=(q['dg'][nxt] if s_ > 0 else None), dh_ext=dh_ext, dc_in=q['dc'][k],
+                                         act=q['act'][tt], c_prev=q['cs'][prev], c=q['cs'][cur], dgates=q['dg'][tt], dc_prev=q['dc'][1 - k]))
+                    elif typ == 'gru':
+                        dirs.append(dict(w_hh_T=q['wT'], dgh_next=(q['dgh'][nxt] if s_ > 0 else None), dh_ext=dh_ext,
+                                         dh_carry_in=(q['carry'][k] if s_ > 0 else None), act=q['act'][tt], h_prev=q['hs'][prev],
+                                         dgi=q['dg'][tt], dgh=q['dgh'][tt], dh_carry_out=q['carry'][1 - k]))
+                    else:
+                        dirs.append(dict(w_hh_T=q['wT'], dg_next=(q['dg'][nxt] if s_ > 0 else None), dh_ext=dh_ext, h=q['hs'][cur], dg=q['dg'][tt]))
+                step(dirs, Hh)
+                k = 1 - k
+            xin = t['enc.in'][l]
+            K = int(xin.shape[1])
+            dxl = dx if l == 0 else self.buf('enc.din.l%d' % l, (T, K), f32, zero=True)
             for di, q in enumerate(st):
-                tt = T - 1 - s_ if di == 0 else s_
-                nxt = tt + 1 if di == 0 else tt - 1               # the step processed just before this one
-                cur, prev = (tt + 1, tt) if di == 0 else (tt, tt + 1)
-                dirs.append(dict(w_hh_T=q['wT'], dgates_next=(q['dg'][nxt] if s_ > 0 else None),
-                                 dh_ext=(dhidden[di * Hh:(di + 1) * Hh] if s_ == 0 else None), dc_in=q['dc'][k], act=q['act'][tt],
-                                 c_prev=q['cs'][prev], c=q['cs'][cur], dgates=q['dg'][tt], dc_prev=q['dc'][1 - k]))
-            O.lstm_step_bwd(dirs, Hh)
-            k = 1 - k
-        for di, q in enumerate(st):
-            sfx, dg, hs = q['sfx'], q['dg'], q['hs']
-            hprev = hs[0:T] if di == 0 else hs[1:T + 1]
-            O.linear_bwd_w(dg, hprev, P.view('rnn_encoder.rnn.weight_hh_l0' + sfx, P.grad), P.view('rnn_encoder.rnn.bias_hh_l0' + sfx, P.grad), T, 4 * Hh, Hh)
-            O.linear_bwd_w(dg, t['enc.x'], P.view('rnn_encoder.rnn.weight_ih_l0' + sfx, P.grad), P.view('rnn_encoder.rnn.bias_ih_l0' + sfx, P.grad), T, 4 * Hh, Hh)
-            self.bwd_x(dg, 'rnn_encoder.rnn.weight_ih_l0' + sfx, dx, T, accumulate=True)
+                key, dg, hs = q['key'], q['dg'], q['hs']
+                dgh = q['dgh'] if typ == 'gru' else dg
+                hprev = hs[0:T] if di == 0 else hs[1:T + 1]
+                O.linear_bwd_w(dgh, hprev, P.view(key('weight_hh'), P.grad), P.view(key('bias_hh'), P.grad), T, G * Hh, Hh)
+                O.linear_bwd_w(dg, xin, P.view(key('weight_ih'), P.grad), P.view(key('bias_ih'), P.grad), T, G * Hh, K)
+                self.bwd_x(dg, key('weight_ih'), dxl, T, accumulate=True)
+            if l > 0:
+                ext = [self.buf('enc.dhext.l%d%s' % (l - 1, sfx), (T, Hh), f32) for sfx in ['', '_reverse'][:ndir]]
+                O.rnn_concat_bwd(dxl, t['enc.ldrop'][l - 1], [dhidden[((l - 1) * ndir + di) * Hh:((l - 1) * ndir + di + 1) * Hh] for di in range(ndir)],
+                                 ext, T, Hh)
         O.act_bwd(dx, t['enc.x'], 1)
-        O.linear_bwd_w(dx, t['enc.emb'], P.view('rnn_encoder.mlp.0.weight', P.grad), P.view('rnn_encoder.mlp.0.bias', P.grad), T, Hh, E)
+        O.linear_bwd_w(dx, t['enc.emb'], P.view('rnn_encoder.mlp.0.weight', P.grad), P.view('rnn_encoder.mlp.0.bias', P.grad), T, WV, E)
         demb = self.buf('enc.demb', (T, E), f32)
         self.bwd_x(dx, 'rnn_encoder.mlp.0.weight', demb, T)
         O.embed_bwd(demb, t['enc.emb'], d['labels'], t['enc.drop'], P.view('rnn_encoder.embedding.weight', P.grad), T, E, False)

@@ -99,9 +99,8 @@ class vgg16(resnetv1):
             e.wb = torch.zeros(K * N, dtype=torch.float32, device=self.device)
             self.extra_transposes.append(e)
             self.wT[name] = (e.wb, N, K)
-        for sfx in ['', '_reverse']:                         # (row-batch data gradients need no copy: resnet_v1.bwd_x)
-            w = 'rnn_encoder.rnn.weight_hh_l0'
-            add(w + sfx, P.view(w + sfx), *P.shapes[w + sfx])
+        for w in self._encoder_hh_keys():                    # (row-batch data gradients need no copy: resnet_v1.bwd_x)
+            add(w, P.view(w), *P.shapes[w])
 
     # ------------------------------------------------------------------ backbone (VGG:53-54,78-82)
     def _backbone_fwd(self, d, saved):

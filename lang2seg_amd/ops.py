@@ -449,6 +449,43 @@ def lstm_step_bwd(dirs, Hh):
     call('l2s_lstm_step_bwd', arr, len(dirs), Hh, stream())
 
 
+def _step(entry, struct, dirs, Hh):
+    arr = (struct * len(dirs))()
+    for i, d in enumerate(dirs):
+        for k, _ in struct._fields_:
+            setattr(arr[i], k, ptr(d.get(k)))
+    call(entry, arr, len(dirs), Hh, stream())
+
+
+def gru_step_fwd(dirs, Hh):
+    """dirs: list (1 or 2) of dicts with the l2s_gru_fwd_dir fields (tensors)"""
+    _step('l2s_gru_step_fwd', _lib.GruFwdDir, dirs, Hh)
+
+
+def gru_step_bwd(dirs, Hh):
+    """l2s_gru_bwd_dir fields; dgh_next / dh_ext / dh_carry_in may be missing or None"""
+    _step('l2s_gru_step_bwd', _lib.GruBwdDir, dirs, Hh)
+
+
+def rnn_step_fwd(dirs, Hh):
+    _step('l2s_rnn_step_fwd', _lib.RnnFwdDir, dirs, Hh)
+
+
+def rnn_step_bwd(dirs, Hh):
+    _step('l2s_rnn_step_bwd', _lib.RnnBwdDir, dirs, Hh)
+
+
+def rnn_concat_fwd(hs, mask, out, T, Hh):
+    """out[T][len(hs) Hh] = the directions' [T][Hh] states side by side (* mask)"""
+    call('l2s_rnn_concat_fwd', ptr(hs[0]), ptr(hs[1]) if len(hs) > 1 else None, ptr(mask), ptr(out), T, Hh, len(hs), stream())
+
+
+def rnn_concat_bwd(dx, mask, adds, ds, T, Hh):
+    """ds[dir][T][Hh] = the halves of dx[T][len(ds) Hh] (* mask), adds[dir] ([Hh] or None) added at the direction's last processed row"""
+    call('l2s_rnn_concat_bwd', ptr(dx), ptr(mask), ptr(adds[0]), ptr(adds[1]) if len(ds) > 1 else None, ptr(ds[0]),
+         ptr(ds[1]) if len(ds) > 1 else None, T, Hh, len(ds), stream())
+
+
 def dynfilter_fwd(x, filt, r, y, resp, respk, H, W, Cc, gate=0):
     call('l2s_dynfilter_fwd', ptr(x), ptr(filt), ptr(r), ptr(y), ptr(resp), ptr(respk), H, W, Cc, dt_of(x), int(gate), stream())
 

@@ -32,6 +32,10 @@ def parse_args(argv=None):
                    'cfg.TEST.NMS, --max_per_image, --det_thresh; box, score, area, COCO RLE mask) as one JSON list to this path (rank suffix as above)')
     p.add_argument('--max_per_image', type=int, default=100, help='--dump_detections: detections kept per sentence over all classes (<= 0: all)')
     p.add_argument('--det_thresh', type=float, default=0.0, help='--dump_detections: a detection needs a score above this')
+    # the expression encoder the snapshot was trained with (tools/opt.py; a snapshot of another encoder is an error that names the flag)
+    # (default None: tools/opt.py's own defaults apply)
+    p.add_argument('--rnn_type', default=None, help='lstm, gru or rnn'); p.add_argument('--rnn_num_layers', type=int, default=None)
+    p.add_argument('--bidirectional', type=int, default=None)
     return vars(p.parse_args(argv))
 
 
@@ -77,6 +81,7 @@ def main(args, variant):
     opt = parse_opt([])
     opt.update(vocab_size=loader.vocab_size, C4_feat_dim=1024, seq_length=loader.label_length,
                dataset_splitBy=args['dataset'] + '_' + args['splitBy'])
+    opt.update({k: args[k] for k in ('rnn_type', 'rnn_num_layers', 'bidirectional') if args.get(k) is not None})
     if args['cfg_file'] and osp.exists(osp.join(ROOT, args['cfg_file'])):
         cfg_from_file(osp.join(ROOT, args['cfg_file']))
     if args['set_cfgs']:

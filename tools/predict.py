@@ -31,6 +31,10 @@ def parse_args(argv=None):
     p.add_argument('--allow_init_weights', type=int, default=0)
     p.add_argument('--all_detections', type=int, default=0); p.add_argument('--max_per_image', type=int, default=100)
     p.add_argument('--det_thresh', type=float, default=0.0)
+    # the expression encoder the snapshot was trained with (tools/opt.py; a snapshot of another encoder is an error that names the flag)
+    # (default None: tools/opt.py's own defaults apply)
+    p.add_argument('--rnn_type', default=None, help='lstm, gru or rnn'); p.add_argument('--rnn_num_layers', type=int, default=None)
+    p.add_argument('--bidirectional', type=int, default=None)
     return vars(p.parse_args(argv))
 
 
@@ -78,6 +82,7 @@ def main(args):
         data = dict(data=blob.cpu().numpy(), im_info=np.array([[oh, ow, sc]], np.float32), file_name=osp.basename(args['image']))
     opt = parse_opt([])
     opt.update(vocab_size=loader.vocab_size, C4_feat_dim=1024, seq_length=loader.label_length, dataset_splitBy=name)
+    opt.update({k: args[k] for k in ('rnn_type', 'rnn_num_layers', 'bidirectional') if args.get(k) is not None})
     if args['variant'] == 'vgg':
         from lang2seg_amd.nets.vgg16 import vgg16
         opt['C4_feat_dim'] = 512
