@@ -380,6 +380,31 @@ int l2s_rnn_step_bwd(const l2s_rnn_bwd_dir* dirs, int ndir, int Hh, hipStream_t 
 int l2s_rnn_concat_fwd(const float* h0, const float* h1, const float* mask, float* out, int T, int Hh, int ndir, hipStream_t s);
 int l2s_rnn_concat_bwd(const float* dx, const float* mask, const float* add0, const float* add1, float* d0, float* d1, int T, int Hh,
                        int ndir, hipStream_t s);
+/* Per-token steps of the top-down attention captioner (AttModel.py:370-395; csrc/topdown_step.hip): nn.LSTMCell arithmetic, gate rows
+ * i, f, g, o, one launch per cell and token, one wave per hidden unit.
+ * A segment is (vector x[n], matrix block w with leading dimension ld); n = 0: unused.
+ * forward : gates[4R] = pre + add0 + add1 (each NULL or [4R]) + sum_k W_k x_k with W_k = rows [4R] x columns [n_k] of a wider matrix
+ *           (seg[k].w points at the block's first column); i, f, o = sigmoid, g = tanh; c = f c_prev + i g; h = o tanh(c);
+ *           stores h[R], c[R] and act[4R] = i, f, g, o.
+ * backward: dh[R] = add0 + add1 (each NULL or [R]) + sum_k T_k v_k with T_k = rows [R] x columns [n_k] of a TRANSPOSED copy;
+ *           dgates[4R] (gradient of the pre-activations) and dc_prev[R] from dc_in (NULL or [R]), act, c_prev, c.
+ * R % 4 != 0, R < 4 or ld < n: error code, nothing launched.  Segments that are not 16-byte aligned take a scalar loop. */
+typedef struct { const float* x; const float* w; int ld; int n; } l2s_topdown_seg;
+typedef struct { const float* pre; const float* add0; const float* add1; l2s_topdown_seg seg[2]; const float* c_prev; float* c; float* h;
+                 float* act; } l2s_topdown_fwd;
+typedef struct { l2s_topdown_seg seg[3]; const float* add0; const float* add1; const float* dc_in; const float* act; const float* c_prev;
+                 const float* c; float* dgates; float* dc_prev; } l2s_topdown_bwd;
+int l2s_topdown_cell_fwd(const l2s_topdown_fwd* a, int R, hipStream_t s);
+int l2s_topdown_cell_bwd(const l2s_topdown_bwd* a, int R, hipStream_t s);
+/* second half of the attention (AttModel.py:419-421) for a feature width R that need not equal att_hid_size: weight[L] = softmax(dots[L]),
+ * att_res[R] = sum_l weight[l] att[l][:]; L <= 256.  (l2s_cap_att_dots_fwd is the first half.) */
+int l2s_cap_att_apply_fwd(const float* att /*[L][R]*/, const float* dots, int L, int R, float* weight, float* att_res, hipStream_t s);
+/* l2s_cap_attention_bwd_step2 with the sum over the locations in its well-conditioned form: datt_h[d] = -aw[d] sum_l ddot[l] (tanh^2[l][d] - m[d]),
+ * m[d] = sum_l weight[l] tanh^2[l][d]; equal to aw[d] sum_l ddot[l] (1 - tanh^2) because sum_l ddot[l] = 0, without that sum's rounding error */
+int l2s_cap_att_bwd_step_centered(const float* dweight, const float* tanh_ws, const float* weight, const float* aw, int L, int D, float* ddot,
+                                  float* datt_h, hipStream_t s);
+/* dst[r][0..cols) = src[r][0..cols) with leading dimensions ldd / lds; lds = 0 repeats one source row */
+int l2s_pack_rows(float* dst, int ldd, const float* src, int lds, int rows, int cols, hipStream_t s);
 /* dynamic-filter correlation (NET:504-562): filt float [7][C] (tanh'ed), r float [7].
  * y(dtype)[HW][C] = x * resp, resp float [HW], respk float [HW][7] (masked per-filter responses) */
 int l2s_dynfilter_fwd(const void* x, const float* filt, const float* r, void* y, float* resp, float* respk, int H, int W, int C,

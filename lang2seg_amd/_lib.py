@@ -67,6 +67,19 @@ class RnnBwdDir(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('w_hh_T', 'dg_next', 'dh_ext', 'h', 'dg')]
 
 
+class TopdownSeg(C.Structure):
+    _fields_ = [('x', vp), ('w', vp), ('ld', i32), ('n', i32)]
+
+
+class TopdownFwd(C.Structure):
+    _fields_ = [('pre', vp), ('add0', vp), ('add1', vp), ('seg', TopdownSeg * 2), ('c_prev', vp), ('c', vp), ('h', vp), ('act', vp)]
+
+
+class TopdownBwd(C.Structure):
+    _fields_ = [('seg', TopdownSeg * 3), ('add0', vp), ('add1', vp), ('dc_in', vp), ('act', vp), ('c_prev', vp), ('c', vp), ('dgates', vp),
+                ('dc_prev', vp)]
+
+
 class Bottleneck64Desc(C.Structure):
     _fields_ = [(n, vp) for n in ('a', 'x', 'w2', 'w3', 'wd', 'w1n', 'b2', 'b3', 'bd', 'b1n', 'y', 'a_next')] + [(n, i32) for n in ('H', 'W', 'Cx')]
 
@@ -188,6 +201,11 @@ SIGS = {
     'l2s_rnn_step_bwd': (i32, [vp, i32, i32, vp]),
     'l2s_rnn_concat_fwd': (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     'l2s_rnn_concat_bwd': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    'l2s_topdown_cell_fwd': (i32, [C.POINTER(TopdownFwd), i32, vp]),
+    'l2s_topdown_cell_bwd': (i32, [C.POINTER(TopdownBwd), i32, vp]),
+    'l2s_cap_att_apply_fwd': (i32, [vp, vp, i32, i32, vp, vp, vp]),
+    'l2s_cap_att_bwd_step_centered': (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    'l2s_pack_rows': (i32, [vp, i32, vp, i32, i32, i32, vp]),
     'l2s_rcnn_predict': (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     'l2s_mask_prob': (i32, [vp, i32, i32, vp, i32, C.c_long, vp, vp]),
     'l2s_response_loss': (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]),

@@ -141,6 +141,7 @@ class SolverWrapper(object):
         # bidirectional - would resume from initialisers without a word)
         if hasattr(self.net, 'P'):
             self.net.P.check_encoder_keys(saved)
+            self.net.P.check_caption_keys(saved)               # ... and so would a snapshot of the other captioner (--caption_model)
         self.load_matched(saved)
         # data parallel: every rank but 0 has its own sidecar (its shard has its own length, permutation and RNG streams); rank 0's file is the
         # reference-format one.  A snapshot written by a single-process or a smaller run lacks some of them.  Whether to go on is decided

@@ -76,6 +76,55 @@ def encoder_rnn_shapes(opt):
     return s
 
 
+CAPTIONERS = ('att2in2', 'topdown')             # caption_models.setup(opt) names seven more; these two are built
+# a tensor only one of the captioners has: tells whose keys a state dict holds
+CAPTIONER_MARK = {'att2in2': 'core.i2h.weight', 'topdown': 'core.att_lstm.weight_ih'}
+
+
+def caption_config(opt):
+    """the captioner `--caption_model` names (caption_models/__init__.py:17-43); ValueError names the option it rejects"""
+    m = str(opt.get('caption_model', 'att2in2'))
+    if m not in CAPTIONERS:
+        raise ValueError('--caption_model %r: the caption branch has %s' % (opt.get('caption_model'), ' and '.join(repr(c) for c in CAPTIONERS)))
+    if m == 'topdown' and (int(opt['rnn_size']) % 4 or int(opt['rnn_size']) < 4):
+        raise ValueError('rnn_size %r: the recurrent kernels of --caption_model topdown need a multiple of 4' % (opt['rnn_size'],))
+    return m
+
+
+def caption_shapes(opt):
+    """torch's own keys and shapes of the captioner's state_dict() under 'caption_model.', in torch's order (ATT:27-57; Att2in2Model deletes
+    fc_embed, ATT:479-484; TopDownCore is two nn.LSTMCell, ATT:370-377)"""
+    m = caption_config(opt)
+    V, R, IE, AH = opt['vocab_size'], opt['rnn_size'], opt['input_encoding_size'], opt['att_hid_size']
+    s = {}
+    s['embed.0.weight'] = (V + 1, IE)
+    if m == 'topdown':
+        s['fc_embed.0.weight'] = (R, opt['fc_feat_size']); s['fc_embed.0.bias'] = (R,)
+    s['att_embed.0.weight'] = (R, opt['att_feat_size']); s['att_embed.0.bias'] = (R,)
+    s['logit.weight'] = (V + 1, R); s['logit.bias'] = (V + 1,)
+    s['ctx2att.weight'] = (AH, R); s['ctx2att.bias'] = (AH,)
+    if m == 'topdown':
+        for cell, K in (('att_lstm', IE + 2 * R), ('lang_lstm', 2 * R)):
+            s['core.%s.weight_ih' % cell] = (4 * R, K); s['core.%s.weight_hh' % cell] = (4 * R, R)
+            s['core.%s.bias_ih' % cell] = (4 * R,); s['core.%s.bias_hh' % cell] = (4 * R,)
+    else:
+        s['core.a2c.weight'] = (2 * R, R); s['core.a2c.bias'] = (2 * R,)
+        s['core.i2h.weight'] = (5 * R, IE); s['core.i2h.bias'] = (5 * R,)
+        s['core.h2h.weight'] = (5 * R, R); s['core.h2h.bias'] = (5 * R,)
+    s['core.attention.h2att.weight'] = (AH, R); s['core.attention.h2att.bias'] = (AH,)
+    s['core.attention.alpha_net.weight'] = (1, AH); s['core.attention.alpha_net.bias'] = (1,)
+    return {'caption_model.' + k: v for k, v in s.items()}
+
+
+def check_caption_keys(opt, keys, prefix='caption_model.'):
+    """`keys` (of a state dict, or of a caption model-best.pth with prefix '') that hold a captioner must hold THIS network's: the other
+    captioner's is an error naming the option to change"""
+    mine = caption_config(opt)
+    for other, mark in CAPTIONER_MARK.items():
+        if other != mine and (prefix + mark) in keys and (prefix + CAPTIONER_MARK[mine]) not in keys:
+            raise ValueError('the state dict holds another captioner; it was trained with --caption_model %s (this network: %s)' % (other, mine))
+
+
 class ParamStore(object):
     def __init__(self, opt, num_layers, num_classes, num_anchors, fixed_blocks, device, dt, variant='cycle'):
         from .variants import VARIANTS
@@ -97,16 +146,7 @@ class ParamStore(object):
         s['rnn_encoder.mlp.0.weight'] = (WV, E); s['rnn_encoder.mlp.0.bias'] = (WV,)
         s.update(encoder_rnn_shapes(o))
         if self.var['cap'] is not None:
-            R, IE, AH = o['rnn_size'], o['input_encoding_size'], o['att_hid_size']
-            s['caption_model.embed.0.weight'] = (V + 1, IE)
-            s['caption_model.att_embed.0.weight'] = (R, o['att_feat_size']); s['caption_model.att_embed.0.bias'] = (R,)
-            s['caption_model.logit.weight'] = (V + 1, R); s['caption_model.logit.bias'] = (V + 1,)
-            s['caption_model.ctx2att.weight'] = (AH, R); s['caption_model.ctx2att.bias'] = (AH,)
-            s['caption_model.core.a2c.weight'] = (2 * R, R); s['caption_model.core.a2c.bias'] = (2 * R,)
-            s['caption_model.core.i2h.weight'] = (5 * R, IE); s['caption_model.core.i2h.bias'] = (5 * R,)
-            s['caption_model.core.h2h.weight'] = (5 * R, R); s['caption_model.core.h2h.bias'] = (5 * R,)
-            s['caption_model.core.attention.h2att.weight'] = (AH, R); s['caption_model.core.attention.h2att.bias'] = (AH,)
-            s['caption_model.core.attention.alpha_net.weight'] = (1, AH); s['caption_model.core.attention.alpha_net.bias'] = (1,)
+            s.update(caption_shapes(o))
 
         def bn(p, c):
             for k in ['weight', 'bias', 'running_mean', 'running_var']:
@@ -372,10 +412,16 @@ class ParamStore(object):
             bad.append('rnn_type / rnn_num_layers / bidirectional / word_vec_size: %s is %s there and %s here' % (diff[0], theirs.get(diff[0]), mine.get(diff[0])))
         raise ValueError('the state dict holds another language encoder; it was trained with ' + ', '.join(bad))
 
+    def check_caption_keys(self, sd):
+        """a state dict that holds a captioner must hold THIS network's (--caption_model); networks without a caption branch take any"""
+        if self.var['cap'] is not None:
+            check_caption_keys(self.opt, sd)
+
     def load_state_dict(self, sd, strict=False):
         """name+shape matched copy (TV:262-281 semantics live in the solver); tolerates missing
         num_batches_tracked and torch-0.3 checkpoints."""
         self.check_encoder_keys(sd)
+        self.check_caption_keys(sd)
         for k, shp in self.shapes.items():
             if k not in sd:
                 if strict:

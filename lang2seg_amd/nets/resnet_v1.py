@@ -13,7 +13,7 @@ from .. import ops as O
 from .._lib import F32, BF16
 from ..model.config import cfg
 from .network import Network, ConvOp, Bottleneck
-from .params import ParamStore, encoder_config
+from .params import ParamStore, encoder_config, caption_config
 from .variants import solver_cfg
 from . import anchors as ANC
 
@@ -32,8 +32,8 @@ class resnetv1(Network):
         self._num_layers = num_layers
         self.opt = dict(opt)
         self.enc = encoder_config(self.opt)      # (rnn_type, layers, directions, gate rows per unit); ValueError names a rejected option
-        if self.var['cap'] is not None:
-            assert self.opt.get('caption_model', 'att2in2') == 'att2in2', 'only the att2in2 captioner is on the hot path'
+        # the captioner --caption_model names ('att2in2' | 'topdown'; ValueError otherwise); networks without a caption branch ignore the option
+        self.cap_model = caption_config(self.opt) if self.var['cap'] is not None else None
         self._cap_loss_weight = float(self.opt.get('cap_loss_weight', 0.0)) if self.var['cap'] is not None else 0.0   # RES:253
         self._C4_feat_dim = self.opt['C4_feat_dim']
 
@@ -131,9 +131,14 @@ class resnetv1(Network):
         # only the matrices whose data gradient is taken one row at a time (inside a recurrence); row batches use bwd_x's MFMA path
         for w in self._encoder_hh_keys():
             add(w, P.view(w), *P.shapes[w])
-        capk = ['caption_model.core.h2h.weight', 'caption_model.core.attention.h2att.weight']
-        if not (self.cap_projected and self.opt['rnn_size'] <= 1024):
-            capk.append('caption_model.core.a2c.weight')     # (the projected-attention recurrence never multiplies by a2c^T row by row)
+        if self.cap_model == 'topdown':
+            # both cells' matrices (att_lstm.weight_ih: its h_lang and fc column blocks, rows of the transposed copy) and h2att
+            capk = ['caption_model.core.%s' % k for k in ('att_lstm.weight_ih', 'att_lstm.weight_hh', 'lang_lstm.weight_ih', 'lang_lstm.weight_hh',
+                                                          'attention.h2att.weight')]
+        else:
+            capk = ['caption_model.core.h2h.weight', 'caption_model.core.attention.h2att.weight']
+            if not (self.cap_projected and self.opt['rnn_size'] <= 1024):
+                capk.append('caption_model.core.a2c.weight')     # (the projected-attention recurrence never multiplies by a2c^T row by row)
         for k in (capk if self.var['cap'] is not None else []):
             add(k, P.view(k), *P.shapes[k])
         # (the dynamic-filter matrix, 7175 x 1024 fp32 = 29 MB, is read as stored by the split NN kernel: no copy)
@@ -321,6 +326,8 @@ class resnetv1(Network):
     # states live in (S+1)-row arrays, row 0 = zeros: h(i) = row i+1, h(i-1) = row i.
     def _caption_pre(self, d):
         """token-only part of _caption_fwd / _caption_bwd, issued early on the language stream"""
+        if self.cap_model == 'topdown':
+            return self._topdown_pre(d)
         P, S = self.P, d['S']
         R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
         pv = lambda k: P.view('caption_model.' + k)
@@ -337,6 +344,8 @@ class resnetv1(Network):
         return pre
 
     def _caption_fwd(self, d, att_feats, loss):
+        if self.cap_model == 'topdown':
+            return self._topdown_fwd(d, att_feats, loss)
         P, t, S = self.P, self.t, d['S']
         pre = getattr(self, '_cap_pre', None)
         R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
@@ -404,6 +413,8 @@ class resnetv1(Network):
 
     def _caption_bwd(self, d, att_feats):
         """returns d(att_feats) in the activation dtype [196][att_feat_size]."""
+        if self.cap_model == 'topdown':
+            return self._topdown_bwd(d, att_feats)
         P, t, S = self.P, self.t, d['S']
         R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
         V1 = self.opt['vocab_size'] + 1
@@ -478,6 +489,177 @@ class resnetv1(Network):
         self.att_embed.wgrad(dadT, att_feats, L, 1, 1)
         datt = self.buf('cap.datt_feats', (L, self.opt['att_feat_size']))
         self.att_embed.dgrad(dadT, L, 1, 1, datt)
+        return datt
+
+    # ------------------------------------------------------------------ top-down captioner (ATT:60-101,370-395,486-490; CRIT:43-53)
+    # Two nn.LSTMCell per token: att_lstm([h_lang(i-1); fc; xt_i]) -> attention(h_att(i)) -> lang_lstm([att_res; h_att(i)]); the output is
+    # h_lang(i).  Per-token launches only (csrc/topdown_step.hip), 5 forward and 5 backward.  States live in (S+1)-row arrays whose row 0 stays
+    # zero: hl / cl / ca row i+1 = step i; `lin` row i+1 = [att_res(i) | h_att(i)], the language cell's input AND the attention cell's state.
+    def _topdown_pre(self, d):
+        """token-only part: dropout masks, word embedding, the xt columns of att_lstm.weight_ih for all S tokens, the zeroed backward buffer"""
+        P, S = self.P, d['S']
+        R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
+        pv = lambda k: P.view('caption_model.' + k)
+        p = self.opt['drop_prob_lm']
+        pre = {'drop_att': self._drop('att', (L, R), p), 'drop_fc': self._drop('fc', (R,), p), 'drop_xt': self._drop('xt', (S, IE), p),
+               'drop_out': self._drop('out', (S, R), p)}
+        xt = self.buf('cap.xt', (S, IE), f32)
+        O.embed_fwd(pv('embed.0.weight'), d['cap_in'], pre['drop_xt'], xt, S, IE, True)
+        Ka = IE + 2 * R
+        xpre = self.buf('td.xpre', (S, 4 * R), f32)
+        O.linear_fwd(xt, pv('core.att_lstm.weight_ih')[2 * R:], pv('core.att_lstm.bias_ih'), xpre, S, 4 * R, IE, ldw=Ka)
+        self.buf('td.bwd_zero', (L * AH + L * R + 4 * R,), f32, zero=True)          # dpatt | dad | sum over tokens of d(att gates)
+        pre.update(xt=xt, xpre=xpre, zeroed=True)
+        return pre
+
+    def _topdown_bufs(self, S):
+        R, AH, L = self.opt['rnn_size'], self.opt['att_hid_size'], 196
+        b = lambda n, shp: self.buf('td.' + n, shp, f32)
+        return dict(hl=b('hl', (S + 1, R)), cl=b('cl', (S + 1, R)), ca=b('ca', (S + 1, R)), lin=b('lin', (S + 1, 2 * R)), act_a=b('act_a', (S, 4 * R)),
+                    act_l=b('act_l', (S, 4 * R)), att_h=b('att_h', (S, AH)), tanh=b('tanh', (S, L, AH)), wgt=b('wgt', (S, L)), dots=b('dots', (S, 256)))
+
+    def _topdown_fwd(self, d, att_feats, loss):
+        P, t, S = self.P, self.t, d['S']
+        pre = getattr(self, '_cap_pre', None) or self._topdown_pre(d)
+        R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
+        V1, FC, Ka = self.opt['vocab_size'] + 1, self.opt['fc_feat_size'], IE + 2 * R
+        pv = lambda k: P.view('caption_model.' + k)
+        a = self.buf('cap.a', (L, R), f32)
+        self.att_embed.fwd(att_feats, L, 1, 1, a, relu=True, out_f32=True)
+        t['cap.a_pre'], t['cap.drop_att'] = a, pre['drop_att']
+        if pre['drop_att'] is not None:
+            ad = self.buf('cap.ad', (L, R), f32); O.mul(a, pre['drop_att'], ad)
+        else:
+            ad = a
+        patt = self.buf('cap.patt', (L, AH), f32)
+        O.linear_fwd(ad, pv('ctx2att.weight'), pv('ctx2att.bias'), patt, L, AH, R)
+        # fc_embed = Linear + ReLU + dropout on the pooled [mean | masked mean] vector, then its columns of att_lstm.weight_ih (+ bias_hh): once
+        fc = t['fc_feats']
+        if fc.dtype != f32:
+            fc32 = self.buf('td.fc32', (FC,), f32); O.cast(fc, fc32)
+        else:
+            fc32 = fc
+        fce = self.buf('td.fce', (R,), f32)
+        O.linear_fwd(fc32, pv('fc_embed.0.weight'), pv('fc_embed.0.bias'), fce, 1, R, FC, act=1)
+        if pre['drop_fc'] is not None:
+            fcd = self.buf('td.fcd', (R,), f32); O.mul(fce, pre['drop_fc'], fcd)
+        else:
+            fcd = fce
+        fcrow = self.buf('td.fcrow', (4 * R,), f32)
+        O.linear_fwd(fcd, pv('core.att_lstm.weight_ih')[R:], pv('core.att_lstm.bias_hh'), fcrow, 1, 4 * R, R, ldw=Ka)
+        B = self._topdown_bufs(S)
+        hl, cl, ca, lin = B['hl'], B['cl'], B['ca'], B['lin']
+        wa_ih, wa_hh, wl_ih, wl_hh = pv('core.att_lstm.weight_ih'), pv('core.att_lstm.weight_hh'), pv('core.lang_lstm.weight_ih'), pv('core.lang_lstm.weight_hh')
+        bl_ih, bl_hh = pv('core.lang_lstm.bias_ih'), pv('core.lang_lstm.bias_hh')
+        h2w, h2b = pv('core.attention.h2att.weight'), pv('core.attention.h2att.bias')
+        aw, ab = pv('core.attention.alpha_net.weight'), pv('core.attention.alpha_net.bias')
+        xpre = pre['xpre']
+        for i in range(S):
+            h_att = lin[i + 1][R:]
+            O.topdown_cell_fwd(xpre[i], fcrow, None, [(hl[i], wa_ih, Ka, R), (lin[i][R:], wa_hh, R, R)], ca[i], ca[i + 1], h_att, B['act_a'][i], R)
+            O.linear_fwd(h_att, h2w, h2b, B['att_h'][i], 1, AH, R)
+            O.cap_att_dots_fwd(patt, B['att_h'][i], aw, ab, L, AH, B['tanh'][i], B['dots'][i])
+            O.cap_att_apply_fwd(ad, B['dots'][i], L, R, B['wgt'][i], lin[i + 1])
+            O.topdown_cell_fwd(None, bl_ih, bl_hh, [(lin[i + 1], wl_ih, 2 * R, 2 * R), (hl[i], wl_hh, R, R)], cl[i], cl[i + 1], hl[i + 1], B['act_l'][i], R)
+        t['cap.drop_out'] = pre['drop_out']
+        if pre['drop_out'] is not None:
+            ho = self.buf('cap.ho', (S, R), f32); O.mul(hl[1:], pre['drop_out'], ho)
+        else:
+            ho = hl[1:]
+        logits = self.buf('cap.logits', (S, V1), f32)
+        O.linear_fwd(ho, pv('logit.weight'), pv('logit.bias'), logits, S, V1, R)
+        dlogits = self.buf('cap.dlogits', (S, V1), f32)
+        lp = self.buf('cap.logp', (S, V1), f32) if self.keep_logprobs else None
+        O.logsoftmax_nll(logits, d['cap_tgt'], d['cap_mask'], S, V1, self._cap_loss_weight, loss[5:6], dlogits, lp)
+        t.update({'cap.ad': ad, 'cap.patt': patt, 'cap.xt': pre['xt'], 'cap.drop_xt': pre['drop_xt'], 'cap.ho': ho, 'cap.dlogits': dlogits, 'cap.logp': lp,
+                  'td.fc32': fc32, 'td.fce': fce, 'td.fcd': fcd, 'td.drop_fc': pre['drop_fc'], 'td.zeroed': pre.get('zeroed')})
+
+    def _topdown_bwd(self, d, att_feats):
+        """returns d(att_feats) in the activation dtype [196][att_feat_size]; d(fc_feats) float [fc_feat_size] is left in self.t['cap.dfc']"""
+        P, t, S = self.P, self.t, d['S']
+        R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
+        V1, FC, Ka = self.opt['vocab_size'] + 1, self.opt['fc_feat_size'], IE + 2 * R
+        pv = lambda k: P.view('caption_model.' + k)
+        gv = lambda k: P.view('caption_model.' + k, P.grad)
+        wT = lambda k: self.wT['caption_model.' + k][0]
+        B = self._topdown_bufs(S)
+        hl, cl, ca, lin = B['hl'], B['cl'], B['ca'], B['lin']
+        dlogits, ad = t['cap.dlogits'], t['cap.ad']
+        later = self._cap_deferred = []           # parameter gradients nothing downstream reads: issued behind the branch's result
+        later.append(lambda: O.linear_bwd_w(dlogits, t['cap.ho'], gv('logit.weight'), gv('logit.bias'), S, V1, R))
+        dho = self.buf('cap.dho', (S, R), f32)
+        self.bwd_x(dlogits, 'caption_model.logit.weight', dho, S, mul=t['cap.drop_out'])
+        nz = L * AH + L * R + 4 * R
+        zb = self.buf('td.bwd_zero', (nz,), f32, zero=not t.get('td.zeroed'))
+        dpatt = zb[:L * AH].view(L, AH); dad = zb[L * AH:L * AH + L * R].view(L, R); dgsum = zb[L * AH + L * R:]
+        b = lambda n, shp: self.buf('td.' + n, shp, f32)
+        dga, dgl, dares, dwl = b('dga', (S, 4 * R)), b('dgl', (S, 4 * R)), b('dares', (S, R)), b('dwl', (S, 256))
+        ddot, datt_h, dca, dcl = b('ddot', (S, L)), b('datt_h', (S, AH)), b('dca', (2, R)), b('dcl', (2, R))
+        ta_ih, ta_hh, tl_ih, tl_hh, th2 = wT('core.att_lstm.weight_ih'), wT('core.att_lstm.weight_hh'), wT('core.lang_lstm.weight_ih'), \
+            wT('core.lang_lstm.weight_hh'), wT('core.attention.h2att.weight')
+        aw = pv('core.attention.alpha_net.weight')
+        G = 4 * R
+        k = 0
+        for i in range(S - 1, -1, -1):
+            last = i == S - 1
+            # language cell: dh = this token's output gradient + what the NEXT token's two cells read of h_lang(i)
+            O.topdown_cell_bwd([] if last else [(dga[i + 1], ta_ih, G, G), (dgl[i + 1], tl_hh, G, G)], dho[i], None, None if last else dcl[k],
+                               B['act_l'][i], cl[i], cl[i + 1], dgl[i], dcl[1 - k], R)
+            # attention: d(att_res) through the first R rows of lang_lstm.weight_ih^T, d(weight) = att . d(att_res), softmax backward + d(att_h)
+            O.linear_fwd(dgl[i], tl_ih, None, dares[i], 1, R, G)
+            O.linear_fwd(dares[i], ad, None, dwl[i], 1, L, R)
+            O.cap_att_bwd_step_centered(dwl[i], B['tanh'][i], B['wgt'][i], aw, L, AH, ddot[i], datt_h[i])
+            # attention cell: dh = the language cell's input + h2att + its own recurrence
+            O.topdown_cell_bwd([(dgl[i], tl_ih[R * G:], G, G), (datt_h[i], th2, AH, AH)] + ([] if last else [(dga[i + 1], ta_hh, G, G)]), None, None,
+                               None if last else dca[k], B['act_a'][i], ca[i], ca[i + 1], dga[i], dca[1 - k], R)
+            k = 1 - k
+        # everything the per-token launches left out of the attention, summed over the S tokens
+        # (alpha_net.bias shifts every score alike and the softmax does not see it: its gradient is 0, and what the launch adds up for it -
+        # sum ddot, pure rounding error - goes to a scratch word instead of the gradient buffer)
+        O.cap_attention_bwd_batched(ddot, B['wgt'], None, R, B['tanh'], aw, S, L, AH, dpatt, dad, gv('core.attention.alpha_net.weight'),
+                                    b('dab_unused', (1,)))
+        O.linear_bwd_w(B['wgt'], dares, dad, None, S, L, R)                     # d(att) += sum_t weight_t (x) d(att_res)_t
+        self.bwd_x(dpatt, 'caption_model.ctx2att.weight', dad, L, accumulate=True)
+        # d(fc_feats): the fc columns see every token's gate gradient, so their sum goes through the transposed block once
+        O.colsum(dga, S, G, G, dgsum)
+        dfcd = self.buf('td.dfcd', (R,), f32)
+        O.linear_fwd(dgsum, ta_ih[R * G:], None, dfcd, 1, R, G)
+        if t['td.drop_fc'] is not None:
+            O.mul(dfcd, t['td.drop_fc'], dfcd)
+        O.act_bwd(dfcd, t['td.fce'], 1)
+        dfc = self.buf('td.dfc', (FC,), f32)
+        self.bwd_x(dfcd, 'caption_model.fc_embed.0.weight', dfc, 1)
+        t['cap.dfc'] = dfc
+
+        def recurrence_grads():
+            # the attention cell's input rows [h_lang(i-1) | fc | xt_i], packed once: its weight gradient is ONE product
+            X = self.buf('td.xatt', (S, Ka), f32, zero=True)
+            if S > 1:
+                O.pack_rows(X[1:], Ka, hl[1:], R, S - 1, R)
+            O.pack_rows(X[:, R:], Ka, t['td.fcd'], 0, S, R)
+            O.pack_rows(X[:, 2 * R:], Ka, t['cap.xt'], IE, S, IE)
+            O.linear_bwd_w(dga, X, gv('core.att_lstm.weight_ih'), gv('core.att_lstm.bias_ih'), S, G, Ka)
+            O.linear_bwd_w(dga, lin[:, R:], gv('core.att_lstm.weight_hh'), gv('core.att_lstm.bias_hh'), S, G, R, ldx=2 * R)
+            O.linear_bwd_w(dgl, lin[1:], gv('core.lang_lstm.weight_ih'), gv('core.lang_lstm.bias_ih'), S, G, 2 * R)
+            O.linear_bwd_w(dgl, hl, gv('core.lang_lstm.weight_hh'), gv('core.lang_lstm.bias_hh'), S, G, R)
+            O.linear_bwd_w(datt_h, lin[1:, R:], gv('core.attention.h2att.weight'), gv('core.attention.h2att.bias'), S, AH, R, ldx=2 * R)
+            O.linear_bwd_w(dfcd, t['td.fc32'], gv('fc_embed.0.weight'), gv('fc_embed.0.bias'), 1, R, FC)
+            dxt = self.buf('cap.dxt', (S, IE), f32)
+            dX = self.buf('td.dxatt', (S, Ka), f32)
+            self.bwd_x(dga, 'caption_model.core.att_lstm.weight_ih', dX, S)
+            O.pack_rows(dxt, IE, dX[:, 2 * R:], Ka, S, IE)
+            O.embed_bwd(dxt, t['cap.xt'], d['cap_in'], t['cap.drop_xt'], gv('embed.0.weight'), S, IE, True)
+            # ctx2att.bias enters the tanh like h2att's output: its gradient is sum_t datt_h[t], whose sum over the locations was taken in the
+            # well-conditioned form; the column sums of dpatt would add that sum's rounding error back
+            O.linear_bwd_w(dpatt, ad, gv('ctx2att.weight'), None, L, AH, R)
+            O.colsum(datt_h, S, AH, AH, gv('ctx2att.bias'))
+        later.append(recurrence_grads)
+        dadT = self.buf('cap.dadT', (L, R))
+        O.mask_relu_cast(dad, t['cap.drop_att'], t['cap.a_pre'], dadT)
+        self.att_embed.wgrad(dadT, att_feats, L, 1, 1)
+        datt = self.buf('cap.datt_feats', (L, self.opt['att_feat_size']))
+        self.att_embed.dgrad(dadT, L, 1, 1, datt)
+        t['cap.datt'] = datt
         return datt
 
     # ------------------------------------------------------------------ backbone / RoI-head hooks (overridden by the VGG variant)
@@ -891,18 +1073,32 @@ class resnetv1(Network):
             feats = l4_on_map(net_conv, 'l4m')
             self._mark('cap: layer4 on map fwd')
             att = self.buf('cap.att', (196, AF))
+            topdown = self.cap_model == 'topdown'
+            if topdown:
+                FC = self.opt['fc_feat_size']
+                if FC != 2 * 2048:
+                    raise ValueError('fc_feat_size %r: fc_feats is the pair of 2048-channel means of layer4 on the map (4096)' % (FC,))
+                fc = t['fc_feats'] = self.buf('cap.fc', (FC,))
             if self.var['cap'] == 'mask':
                 gm = self.buf('cap.gm', (HW,), f32)
                 O.mask_downsample(d['gt_masks'], gm, H, W, Hc, Wc)
                 O.adaptive_pool_fwd(feats, None, att, Hc, Wc, 2048, 14, 14, AF)
                 O.adaptive_pool_fwd(feats, gm, att[:, 2048:], Hc, Wc, 2048, 14, 14, AF)
                 t.update({'feats_all': feats, 'att_feats': att, 'gt_mask_small': gm})
+                if topdown:
+                    # fc_feats = [mean of the map | mean of the masked map] (NET:418,431,434): the same pooling with ONE output bin
+                    O.adaptive_pool_fwd(feats, None, fc, Hc, Wc, 2048, 1, 1, FC)
+                    O.adaptive_pool_fwd(feats, gm, fc[2048:], Hc, Wc, 2048, 1, 1, FC)
             else:
                 # cycle_response: [layer4(map before the gating) ; layer4(gated map)] (network_cycle_response.py:425-439)
                 feats_b = l4_on_map(base, 'l4b')
                 O.adaptive_pool_fwd(feats_b, None, att, Hc, Wc, 2048, 14, 14, AF)
                 O.adaptive_pool_fwd(feats, None, att[:, 2048:], Hc, Wc, 2048, 14, 14, AF)
                 t.update({'feats_all': feats, 'feats_before_all': feats_b, 'att_feats': att})
+                if topdown:
+                    # fc_feats = [mean before the gating | mean after] (network_cycle_response.py:428,431,438)
+                    O.adaptive_pool_fwd(feats_b, None, fc, Hc, Wc, 2048, 1, 1, FC)
+                    O.adaptive_pool_fwd(feats, None, fc[2048:], Hc, Wc, 2048, 1, 1, FC)
             self._mark('cap: pools')
             yield
             self._caption_fwd(d, att, loss)
@@ -923,8 +1119,21 @@ class resnetv1(Network):
                     self._mark('cap: deferred parameter gradients (lang)')
                 self._cap_deferred = []
             g = self.buf('l4m.g', (HW, 2048))
+
+            def fc_grad():
+                """d(fc_feats) of the top-down captioner in the activation dtype"""
+                dfc32 = t['cap.dfc']
+                if self.dt == F32:
+                    return dfc32
+                dfc = self.buf('cap.dfc_dt', (FC,)); O.cast(dfc32, dfc)
+                return dfc
             if self.var['cap'] == 'mask':
                 O.adaptive_pool_bwd(datt, AF, 0, 2048, gm, g, feats, Hc, Wc, 2048, 14, 14)
+                if topdown:
+                    # d(fc_feats) joins d(feats) before layer4's data gradient: the one-bin pooling backward, added to the 14x14 one
+                    dfc, g2 = fc_grad(), self.buf('l4m.gfc', (HW, 2048))
+                    O.adaptive_pool_bwd(dfc, FC, 0, 2048, gm, g2, feats, Hc, Wc, 2048, 1, 1)
+                    O.add3(g, g2, None, g)
                 r = l4_on_map_bwd(g, 'l4m')
                 self._mark('cap: pool bwd + layer4 on map dgrad')
                 deferred_grads()
@@ -932,6 +1141,12 @@ class resnetv1(Network):
             gb = self.buf('l4b.g', (HW, 2048))
             O.adaptive_pool_bwd(datt, AF, 0, 0, None, gb, feats_b, Hc, Wc, 2048, 14, 14)
             O.adaptive_pool_bwd(datt, AF, 2048, 0, None, g, feats, Hc, Wc, 2048, 14, 14)
+            if topdown:
+                dfc, g2 = fc_grad(), self.buf('l4m.gfc', (HW, 2048))
+                O.adaptive_pool_bwd(dfc, FC, 0, 0, None, g2, feats_b, Hc, Wc, 2048, 1, 1)
+                O.add3(gb, g2, None, gb)
+                O.adaptive_pool_bwd(dfc, FC, 2048, 0, None, g2, feats, Hc, Wc, 2048, 1, 1)
+                O.add3(g, g2, None, g)
             d_base_cap = l4_on_map_bwd(gb, 'l4b', in_relu=True)
             r = l4_on_map_bwd(g, 'l4m')
             deferred_grads()

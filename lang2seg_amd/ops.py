@@ -475,6 +475,49 @@ def rnn_step_bwd(dirs, Hh):
     _step('l2s_rnn_step_bwd', _lib.RnnBwdDir, dirs, Hh)
 
 
+def _topdown_segs(arr, segs):
+    for q, sg in zip(arr, segs):
+        if sg is not None:
+            x, w, ld, n = sg
+            q.x, q.w, q.ld, q.n = ptr(x), ptr(w), int(ld), int(n)
+
+
+def topdown_cell_fwd(pre, add0, add1, segs, c_prev, c, h, act, R):
+    """one nn.LSTMCell step (csrc/topdown_step.hip): gates = pre + add0 + add1 + sum over segs (x[n], w, ld, n) of w[4R][:n] . x, with w a
+    column block (leading dimension ld) of a wider matrix; writes h, c and act[4R] = i, f, g, o.  Up to two segments; None entries are skipped."""
+    a = _lib.TopdownFwd()
+    a.pre, a.add0, a.add1, a.c_prev, a.c, a.h, a.act = ptr(pre), ptr(add0), ptr(add1), ptr(c_prev), ptr(c), ptr(h), ptr(act)
+    assert len(segs) <= 2
+    _topdown_segs(a.seg, segs)
+    call('l2s_topdown_cell_fwd', C.byref(a), int(R), stream())
+
+
+def topdown_cell_bwd(segs, add0, add1, dc_in, act, c_prev, c, dgates, dc_prev, R):
+    """the matching backward step: dh = add0 + add1 + sum over segs (v[n], wT, ld, n) of wT[R][:n] . v (blocks of transposed copies), then
+    dgates[4R] and dc_prev[R].  Up to three segments."""
+    a = _lib.TopdownBwd()
+    a.add0, a.add1, a.dc_in, a.act, a.c_prev, a.c, a.dgates, a.dc_prev = (ptr(add0), ptr(add1), ptr(dc_in), ptr(act), ptr(c_prev), ptr(c),
+                                                                           ptr(dgates), ptr(dc_prev))
+    assert len(segs) <= 3
+    _topdown_segs(a.seg, segs)
+    call('l2s_topdown_cell_bwd', C.byref(a), int(R), stream())
+
+
+def cap_att_apply_fwd(att, dots, L, R, weight, att_res):
+    """weight[L] = softmax(dots), att_res[R] = weight . att[L][R]"""
+    call('l2s_cap_att_apply_fwd', ptr(att), ptr(dots), L, R, ptr(weight), ptr(att_res), stream())
+
+
+def cap_att_bwd_step_centered(dweight, tanh_ws, weight, aw, L, D, ddot, datt_h):
+    """cap_attention_bwd_step2 with the sum over the locations centred on its weighted mean (csrc/topdown_step.hip)"""
+    call('l2s_cap_att_bwd_step_centered', ptr(dweight), ptr(tanh_ws), ptr(weight), ptr(aw), L, D, ptr(ddot), ptr(datt_h), stream())
+
+
+def pack_rows(dst, ldd, src, lds, rows, cols):
+    """dst[r][:cols] = src[r][:cols] (leading dimensions ldd / lds; lds = 0 repeats one source row)"""
+    call('l2s_pack_rows', ptr(dst), int(ldd), ptr(src), int(lds), int(rows), int(cols), stream())
+
+
 def rnn_concat_fwd(hs, mask, out, T, Hh):
     """out[T][len(hs) Hh] = the directions' [T][Hh] states side by side (* mask)"""
     call('l2s_rnn_concat_fwd', ptr(hs[0]), ptr(hs[1]) if len(hs) > 1 else None, ptr(mask), ptr(out), T, Hh, len(hs), stream())

@@ -94,6 +94,8 @@ def load_caption_weights(net, opt, root='.'):
         sd = torch.load(f, map_location='cpu', weights_only=True)        # tensors only: no arbitrary unpickling
     except TypeError:
         sd = torch.load(f, map_location='cpu')
+    from ..nets.params import check_caption_keys
+    check_caption_keys(opt, sd, prefix='')                 # the other captioner's file: ValueError naming --caption_model
     cur = net.state_dict()
     own = {k[len('caption_model.'):]: k for k in cur if k.startswith('caption_model.')}
     missing = sorted(set(own) - set(sd)); unexpected = sorted(set(sd) - set(own))
