@@ -380,7 +380,7 @@ int l2s_rnn_step_bwd(const l2s_rnn_bwd_dir* dirs, int ndir, int Hh, hipStream_t 
 int l2s_rnn_concat_fwd(const float* h0, const float* h1, const float* mask, float* out, int T, int Hh, int ndir, hipStream_t s);
 int l2s_rnn_concat_bwd(const float* dx, const float* mask, const float* add0, const float* add1, float* d0, float* d1, int T, int Hh,
                        int ndir, hipStream_t s);
-/* Per-token steps of the top-down attention captioner (AttModel.py:370-395; csrc/topdown_step.hip): nn.LSTMCell arithmetic, gate rows
+/* Per-token steps of the top-down attention captioner (AttModel.py:370-395; csrc/caption_step.hip): nn.LSTMCell arithmetic, gate rows
  * i, f, g, o, one launch per cell and token, one wave per hidden unit.
  * A segment is (vector x[n], matrix block w with leading dimension ld); n = 0: unused.
  * forward : gates[4R] = pre + add0 + add1 (each NULL or [4R]) + sum_k W_k x_k with W_k = rows [4R] x columns [n_k] of a wider matrix
@@ -438,7 +438,7 @@ int l2s_linear_sum2_fwd(const float* x1, const float* w1 /*[N][K1]*/, int K1, co
                         int accumulate, hipStream_t s);
 int l2s_cap_a2c_gates_fwd(const float* att_res, const float* w_a2c /*[2R][K]*/, const float* b_a2c, int K, const float* sums /*[5R]*/,
                           const float* c_prev, float* c, float* h, float* save /*[6R]*/, int R, hipStream_t s);
-/* Projected-attention form of the same step (csrc/lang.hip): P = att . W_a2c^T [L][2R] once per sentence, then per token
+/* Projected-attention form of the same step (csrc/caption_step.hip): P = att . W_a2c^T [L][2R] once per sentence, then per token
  *   l2s_cap_att_dots_fwd      : dots[l] = alpha . tanh(patt[l] + att_h) + b                                  (ATT:411-418)
  *   l2s_cap_apply_gates_fwd   : softmax(dots) -> weight[L]; a2c = sum_l weight[l] P[l] + b_a2c; gates / cell update  (ATT:419-423,449-462)
  *   l2s_cap_gates_bwd_dw      : gate backward (as l2s_cap_gates_bwd) + dweight[l] = P[l] . da2c

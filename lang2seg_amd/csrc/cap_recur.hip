@@ -1,6 +1,6 @@
 // The att2in2 captioner recurrence (lib/caption_models/AttModel.py:406-423 attention, 446-466 core) as ONE resident launch per direction.
 //
-// Until round 5 a token cost three dependent launches each way (h GEMVs -> attention dots -> softmax . P + gates; lang.hip), 16.6 us of
+// Until round 5 a token cost three dependent launches each way (h GEMVs -> attention dots -> softmax . P + gates; caption_step.hip), 16.6 us of
 // kernel time and 32 us of wall per token inside the step: launch boundaries and queue waits on the critical chain of the caption
 // branch.  Here 32 workgroups of 512 threads stay resident for the whole sentence, partition the work BY HIDDEN UNIT and exchange three
 // small vectors per token with the all-gather primitive tools/cap_allgather_probe.hip priced (1.4 us on an idle chip, 2.1-2.4 us beside
@@ -28,6 +28,7 @@
 //      32 x 512 granules, each workgroup sums the 32 partial vectors of its 16 units in producer order (bit-reproducible).
 #include "common.h"
 #include "../../include/lang2seg_hip.h"
+#include "recur.h"
 
 namespace {
 
@@ -39,7 +40,6 @@ constexpr int NWG = L2S_CAP_RECUR_WGS, NT = 512, R = 512, AH = 512, UPW = 16, LP
 constexpr unsigned SPIN_LIMIT = 1u << 20;
 constexpr size_t LDS_REQ = 152 * 1024;     // owns the CU's LDS: no LDS-using workgroup of another queue co-resides (the price of an exchange doubles to triples otherwise)
 
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ void put(gu64* g, unsigned tag, float v) { __hip_atomic_store(g, ((u64)tag << 32) | __float_as_uint(v), RLX_AGENT); }
 
 // every thread of the workgroup polls granules tid, tid + NT, ... (NR per thread) of g[0, n) until their tags match, then dst[i] = value.
@@ -198,17 +198,12 @@ __global__ __launch_bounds__(NT) void cap_recur_fwd_kernel(l2s_cap_recur_fwd_arg
       float a0 = ba0, a1 = ba1;
 #pragma unroll
       for (int g = 0; g < 16; ++g) { a0 += part[g * 32 + tid]; a1 += part[g * 32 + 16 + tid]; }
-      const float ig = sigm(sg[0] + s_l[tid]), fg = sigm(sg[1] + s_l[16 + tid]), og = sigm(sg[2] + s_l[32 + tid]);
-      const float t0 = sg[3] + s_l[48 + tid] + a0, t1 = sg[4] + s_l[64 + tid] + a1;
-      const float it = fmaxf(t0, t1);
-      const float cn = fg * c_prev + ig * it;
-      const float tc = tanhf(cn);
-      const float hn = og * tc;
+      const float sj[5] = {sg[0] + s_l[tid], sg[1] + s_l[16 + tid], sg[2] + s_l[32 + tid], sg[3] + s_l[48 + tid], sg[4] + s_l[64 + tid]};
+      float sv[6], cn, hn;
+      att2in_gates_fwd(sj, a0, a1, c_prev, cn, hn, sv);
       if (t + 1 < S) put(G3 + j, tag + 2, hn);
       a.cs[(long)(t + 1) * R + j] = cn; a.hs[(long)(t + 1) * R + j] = hn;
-      float* sv = a.save + (long)t * 6 * R;
-      sv[j] = ig; sv[R + j] = fg; sv[2 * R + j] = og; sv[3 * R + j] = (t0 >= t1) ? 0.f : 1.f;     // torch.max(a, b): first wins ties
-      sv[4 * R + j] = it; sv[5 * R + j] = tc;
+      st_rows<6>(a.save + (long)t * 6 * R, R, j, sv);
       c_prev = cn;
       if (t + 1 < S) {
 #pragma unroll
@@ -264,22 +259,15 @@ __global__ __launch_bounds__(NT) void cap_recur_bwd_kernel(l2s_cap_recur_bwd_arg
     for (int k = 0; k < 4; ++k) wq[k] = lane + 64 * k < L ? a.wgt[(long)t * L + lane + 64 * k] : 0.f;
 #pragma unroll
     for (int q = 0; q < 7; ++q) { const int l = lg + 32 * q; tq[q] = l < L ? a.tanh_ws[((long)t * L + l) * AH + UPW * w + jj] : 1.f; }
-    // ---- 1: gate backward of the own units (cap_gates_bwd_kernel's arithmetic) ----
+    // ---- 1: gate backward of the own units ----
     if (tid < UPW) {
-      const float* sv = a.save + (long)t * 6 * R;
-      const float ig = sv[j], fg = sv[R + j], og = sv[2 * R + j], sel = sv[3 * R + j], it = sv[4 * R + j], tc = sv[5 * R + j];
-      const float dhj = dh + a.dho[(long)t * R + j];       // recurrent part + this step's output gradient
-      const float dcn = dc + dhj * og * (1.f - tc * tc);
-      const float d0s = dcn * it * ig * (1.f - ig), d1s = dcn * a.cs[(long)t * R + j] * fg * (1.f - fg), d2s = dhj * tc * og * (1.f - og);
-      const float dit = dcn * ig;
-      const float d0 = sel == 0.f ? dit : 0.f, d1 = sel == 0.f ? 0.f : dit;
-      put(G1 + j, tag, d0); put(G1 + R + j, tag, d1);
-      float* ds = a.dsums + (long)t * 5 * R;
-      ds[j] = d0s; ds[R + j] = d1s; ds[2 * R + j] = d2s; ds[3 * R + j] = d0; ds[4 * R + j] = d1;
-      float* da = a.da2c + (long)t * 2 * R;
-      da[j] = d0; da[R + j] = d1;
-      v_l[jj] = d0s; v_l[16 + jj] = d1s; v_l[32 + jj] = d2s; v_l[48 + jj] = d0; v_l[64 + jj] = d1;
-      dc = dcn * fg;
+      float sv[6], dv[5];                                  // dv: the five d(sums) rows of the unit (the last two are d(a2c))
+      ld_rows<6>(sv, a.save + (long)t * 6 * R, R, j);
+      att2in_gates_bwd(sv, dh + a.dho[(long)t * R + j], dc, a.cs[(long)t * R + j], dv, dv[3], dv[4], dc);
+      put(G1 + j, tag, dv[3]); put(G1 + R + j, tag, dv[4]);
+      st_rows<5>(a.dsums + (long)t * 5 * R, R, j, dv);
+      st_rows<2>(a.da2c + (long)t * 2 * R, R, j, dv + 3);
+      st_rows<5>(v_l, 16, jj, dv);
     }
     if (!gather<2>(G1, 2 * R, tag, g_l, dead, state + 1)) { a.dsums[tid] = NAN; if (w == 0 && tid == 0) state[0] = state[0] + 1u; return; }      // a give-up poisons d(sums): the captioner's gradients turn NaN
     // ---- 2: d(weight) of the own locations: P[l] . d(a2c), one wave each ----
@@ -290,7 +278,7 @@ __global__ __launch_bounds__(NT) void cap_recur_bwd_kernel(l2s_cap_recur_bwd_arg
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const float4 pv = *(const float4*)(prow_l + wv * 1024 + q * 256 + lane * 4), gv = *(const float4*)(g_l + q * 256 + lane * 4);
-          acc = fmaf(pv.x, gv.x, fmaf(pv.y, gv.y, fmaf(pv.z, gv.z, fmaf(pv.w, gv.w, acc))));
+          acc = dot4(pv, gv, acc);
         }
         acc = wave_sum(acc);
         if (lane == 0) put(G2 + l, tag + 1, acc);

@@ -42,7 +42,7 @@ __device__ __forceinline__ void stx(void* p, long i, int dt, float v) {
 }
 
 // Wave-wide reductions on the DPP path (no LDS traffic: the ds_bpermute butterflies these replace cost six LDS round trips per sum, and
-// their results must not be consumed behind a younger LDS write, see lang.hip cap_att_bwd_step_kernel): a scan inside each row of 16
+// their results must not be consumed behind a younger LDS write, see caption_step.hip cap_att_bwd_step_kernel): a scan inside each row of 16
 // lanes (row_shr 1, 2, 4, 8), then row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3; lane 63 holds the result and is
 // broadcast.  The result is the same in every lane; the summation order is fixed.
 template <int CTRL, int ROW_MASK>

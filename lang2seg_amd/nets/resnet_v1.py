@@ -322,7 +322,65 @@ class resnetv1(Network):
         self.bwd_x(dx, 'rnn_encoder.mlp.0.weight', demb, T)
         O.embed_bwd(demb, t['enc.emb'], d['labels'], t['enc.drop'], P.view('rnn_encoder.embedding.weight', P.grad), T, E, False)
 
-    # ------------------------------------------------------------------ att2in2 captioner (ATT:60-101,406-466; CRIT:43-53)
+    # ------------------------------------------------------------------ head and tail of both captioners (ATT:60-101; CRIT:43-53)
+    def _cap_head_fwd(self, pre, att_feats):
+        """att_embed (Linear + ReLU on the 196 attention features) -> attention dropout -> ctx2att: (ad [196][rnn_size], patt [196][att_hid_size])"""
+        t = self.t
+        R, AH, L = self.opt['rnn_size'], self.opt['att_hid_size'], 196
+        a = self.buf('cap.a', (L, R), f32)
+        self.att_embed.fwd(att_feats, L, 1, 1, a, relu=True, out_f32=True)
+        t['cap.a_pre'], t['cap.drop_att'] = a, pre['drop_att']
+        if pre['drop_att'] is not None:
+            ad = self.buf('cap.ad', (L, R), f32); O.mul(a, pre['drop_att'], ad)
+        else:
+            ad = a
+        patt = self.buf('cap.patt', (L, AH), f32)
+        O.linear_fwd(ad, self.P.view('caption_model.ctx2att.weight'), self.P.view('caption_model.ctx2att.bias'), patt, L, AH, R)
+        return ad, patt
+
+    def _cap_tail_fwd(self, d, pre, h, ad, patt, loss):
+        """the recurrence's outputs h [S][rnn_size] -> output dropout -> logits -> log-softmax + masked NLL into loss[5]"""
+        t, S = self.t, d['S']
+        R, V1 = self.opt['rnn_size'], self.opt['vocab_size'] + 1
+        t['cap.drop_out'] = pre['drop_out']
+        if pre['drop_out'] is not None:
+            ho = self.buf('cap.ho', (S, R), f32); O.mul(h, pre['drop_out'], ho)
+        else:
+            ho = h
+        logits = self.buf('cap.logits', (S, V1), f32)
+        O.linear_fwd(ho, self.P.view('caption_model.logit.weight'), self.P.view('caption_model.logit.bias'), logits, S, V1, R)
+        dlogits = self.buf('cap.dlogits', (S, V1), f32)
+        lp = self.buf('cap.logp', (S, V1), f32) if self.keep_logprobs else None
+        O.logsoftmax_nll(logits, d['cap_tgt'], d['cap_mask'], S, V1, self._cap_loss_weight, loss[5:6], dlogits, lp)
+        t.update({'cap.ad': ad, 'cap.patt': patt, 'cap.xt': pre['xt'], 'cap.drop_xt': pre['drop_xt'], 'cap.ho': ho, 'cap.dlogits': dlogits, 'cap.logp': lp})
+
+    def _cap_head_bwd(self, S):
+        """-> (later, dho).  Only d(att_feats) is on the step's critical path (the main queue waits for it at the caption join): the parameter
+        gradients that nothing downstream reads are collected in `later` and issued after the branch has produced its result (caption_branch:
+        on the language stream, behind the join point); the logit layer's is the first.  dho [S][rnn_size]: d(outputs of the recurrence)"""
+        t = self.t
+        R, V1 = self.opt['rnn_size'], self.opt['vocab_size'] + 1
+        gv = lambda k: self.P.view('caption_model.' + k, self.P.grad)
+        dlogits = t['cap.dlogits']
+        later = self._cap_deferred = []
+        later.append(lambda: O.linear_bwd_w(dlogits, t['cap.ho'], gv('logit.weight'), gv('logit.bias'), S, V1, R))
+        dho = self.buf('cap.dho', (S, R), f32)
+        self.bwd_x(dlogits, 'caption_model.logit.weight', dho, S, mul=t['cap.drop_out'])
+        return later, dho
+
+    def _cap_tail_bwd(self, dad, att_feats):
+        """d(ad) [196][rnn_size], complete -> d(att_feats) in the activation dtype [196][att_feat_size] through att_embed"""
+        t = self.t
+        R, L = self.opt['rnn_size'], 196
+        dadT = self.buf('cap.dadT', (L, R))
+        # dropout mask (it multiplies the accumulated sum, not only this term), ReLU backward and the cast to the activation dtype: one launch
+        O.mask_relu_cast(dad, t['cap.drop_att'], t['cap.a_pre'], dadT)
+        self.att_embed.wgrad(dadT, att_feats, L, 1, 1)
+        datt = self.buf('cap.datt_feats', (L, self.opt['att_feat_size']))
+        self.att_embed.dgrad(dadT, L, 1, 1, datt)
+        return datt
+
+    # ------------------------------------------------------------------ att2in2 captioner (ATT:406-466)
     # states live in (S+1)-row arrays, row 0 = zeros: h(i) = row i+1, h(i-1) = row i.
     def _caption_pre(self, d):
         """token-only part of _caption_fwd / _caption_bwd, issued early on the language stream"""
@@ -347,36 +405,18 @@ class resnetv1(Network):
         if self.cap_model == 'topdown':
             return self._topdown_fwd(d, att_feats, loss)
         P, t, S = self.P, self.t, d['S']
-        pre = getattr(self, '_cap_pre', None)
-        R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
-        V1 = self.opt['vocab_size'] + 1
+        pre = getattr(self, '_cap_pre', None) or self._caption_pre(d)
+        R, AH, L = self.opt['rnn_size'], self.opt['att_hid_size'], 196
         SC = 256                                             # per-row scratch tail of the attention kernels
         pv = lambda k: P.view('caption_model.' + k)
-        a = self.buf('cap.a', (L, R), f32)
-        self.att_embed.fwd(att_feats, L, 1, 1, a, relu=True, out_f32=True)
-        t['cap.a_pre'] = a
-        dm = pre['drop_att'] if pre else self._drop('att', (L, R), self.opt['drop_prob_lm'])
-        t['cap.drop_att'] = dm
-        if dm is not None:
-            ad = self.buf('cap.ad', (L, R), f32); O.mul(a, dm, ad)
-        else:
-            ad = a
-        patt = self.buf('cap.patt', (L, AH), f32)
-        O.linear_fwd(ad, pv('ctx2att.weight'), pv('ctx2att.bias'), patt, L, AH, R)
-        if pre:
-            xt, sums, t['cap.drop_xt'] = pre['xt'], pre['sums'], pre['drop_xt']
-        else:
-            xt = self.buf('cap.xt', (S, IE), f32)
-            t['cap.drop_xt'] = self._drop('xt', (S, IE), self.opt['drop_prob_lm'])
-            O.embed_fwd(pv('embed.0.weight'), d['cap_in'], t['cap.drop_xt'], xt, S, IE, True)
-            sums = self.buf('cap.sums', (S, 5 * R), f32)
-            O.linear_fwd(xt, pv('core.i2h.weight'), pv('core.i2h.bias'), sums, S, 5 * R, IE)
+        ad, patt = self._cap_head_fwd(pre, att_feats)
+        sums = pre['sums']
         hs = self.buf('cap.hfull', (S + 1, R), f32); cs = self.buf('cap.cfull', (S + 1, R), f32); save = self.buf('cap.save', (S, 6 * R), f32)
         att_h = self.buf('cap.att_h', (S, AH), f32); tanh_ws = self.buf('cap.tanh', (S, L, AH), f32)
         wgt = self.buf('cap.wgt', (S, L), f32); ares = self.buf('cap.ares', (S, R + SC), f32); a2c = self.buf('cap.a2c', (S, 2 * R), f32)
         proj = self.cap_projected and R <= 1024
         if proj:
-            # projected attention (csrc/lang.hip): P = att . W_a2c^T once, then 3 launches per token
+            # projected attention (csrc/caption_step.hip): P = att . W_a2c^T once, then 3 launches per token
             Pm = self.buf('cap.P', (L, 2 * R), f32); dots = self.buf('cap.dots', (S, 256), f32)
             O.linear_fwd(ad, pv('core.a2c.weight'), None, Pm, L, 2 * R, R)
             t['cap.P'] = Pm
@@ -399,17 +439,8 @@ class resnetv1(Network):
             O.cap_attention_fwd(patt, ad, att_h[i], pv('core.attention.alpha_net.weight'), pv('core.attention.alpha_net.bias'), L, AH,
                                 tanh_ws[i], wgt[i], ares[i])
             O.cap_a2c_gates_fwd(ares[i], pv('core.a2c.weight'), pv('core.a2c.bias'), R, sums[i], cs[i], cs[i + 1], hs[i + 1], save[i], R)
-        t['cap.drop_out'] = pre['drop_out'] if pre else self._drop('out', (S, R), self.opt['drop_prob_lm'])
-        if t['cap.drop_out'] is not None:
-            ho = self.buf('cap.ho', (S, R), f32); O.mul(hs[1:], t['cap.drop_out'], ho)
-        else:
-            ho = hs[1:]
-        logits = self.buf('cap.logits', (S, V1), f32)
-        O.linear_fwd(ho, pv('logit.weight'), pv('logit.bias'), logits, S, V1, R)
-        dlogits = self.buf('cap.dlogits', (S, V1), f32)
-        lp = self.buf('cap.logp', (S, V1), f32) if self.keep_logprobs else None
-        O.logsoftmax_nll(logits, d['cap_tgt'], d['cap_mask'], S, V1, self._cap_loss_weight, loss[5:6], dlogits, lp)
-        t.update({'cap.ad': ad, 'cap.patt': patt, 'cap.xt': xt, 'cap.ho': ho, 'cap.dlogits': dlogits, 'cap.logp': lp})
+        self._cap_tail_fwd(d, pre, hs[1:], ad, patt, loss)
+        t['cap.zeroed'] = pre.get('zeroed')
 
     def _caption_bwd(self, d, att_feats):
         """returns d(att_feats) in the activation dtype [196][att_feat_size]."""
@@ -417,27 +448,20 @@ class resnetv1(Network):
             return self._topdown_bwd(d, att_feats)
         P, t, S = self.P, self.t, d['S']
         R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
-        V1 = self.opt['vocab_size'] + 1
         SC = 256
         pv = lambda k: P.view('caption_model.' + k)
         gv = lambda k: P.view('caption_model.' + k, P.grad)
         hs = self.buf('cap.hfull', (S + 1, R), f32); cs = self.buf('cap.cfull', (S + 1, R), f32); save = self.buf('cap.save', (S, 6 * R), f32)
         tanh_ws = self.buf('cap.tanh', (S, L, AH), f32); wgt = self.buf('cap.wgt', (S, L), f32)
         ares = self.buf('cap.ares', (S, R + SC), f32)
-        dlogits, ad = t['cap.dlogits'], t['cap.ad']
-        # Only d(att_feats) is on the step's critical path (the main queue waits for it at the caption join): the parameter
-        # gradients that nothing downstream reads are collected in `later` and issued after the branch has produced its result
-        # (caption_branch: on the language stream, behind the join point).
-        later = self._cap_deferred = []
-        later.append(lambda: O.linear_bwd_w(dlogits, t['cap.ho'], gv('logit.weight'), gv('logit.bias'), S, V1, R))
-        dho = self.buf('cap.dho', (S, R), f32)
-        self.bwd_x(dlogits, 'caption_model.logit.weight', dho, S, mul=t['cap.drop_out'])
+        ad = t['cap.ad']
+        later, dho = self._cap_head_bwd(S)
         dsums = self.buf('cap.dsums', (S, 5 * R), f32); da2c = self.buf('cap.da2c', (S, 2 * R), f32)
         datt_h = self.buf('cap.datt_h', (S, AH + SC), f32); dares = self.buf('cap.dares', (S, R), f32); ddot = self.buf('cap.ddot', (S, L), f32)
         proj = self.cap_projected and R <= 1024
         # dpatt | dad | dh | dc (| dP): one buffer, one clear
         nz = L * AH + L * R + 4 * R
-        zb = self.buf('cap.bwd_zero', (nz + (L * 2 * R if proj else 0),), f32, zero=not (getattr(self, '_cap_pre', None) or {}).get('zeroed'))
+        zb = self.buf('cap.bwd_zero', (nz + (L * 2 * R if proj else 0),), f32, zero=not t.get('cap.zeroed'))
         dpatt = zb[:L * AH].view(L, AH); dad = zb[L * AH:L * AH + L * R].view(L, R)
         dh = zb[L * AH + L * R:L * AH + L * R + 2 * R].view(2, R); dc = zb[L * AH + L * R + 2 * R:nz].view(2, R)
         wT_h2h = self.wT['caption_model.core.h2h.weight'][0]; wT_h2att = self.wT['caption_model.core.attention.h2att.weight'][0]
@@ -483,17 +507,11 @@ class resnetv1(Network):
         later.append(recurrence_grads)
         # ctx2att
         self.bwd_x(dpatt, 'caption_model.ctx2att.weight', dad, L, accumulate=True)
-        dadT = self.buf('cap.dadT', (L, R))
-        # dropout mask (it multiplies the accumulated sum, not only this term), ReLU backward and the cast to the activation dtype: one launch
-        O.mask_relu_cast(dad, t['cap.drop_att'], t['cap.a_pre'], dadT)
-        self.att_embed.wgrad(dadT, att_feats, L, 1, 1)
-        datt = self.buf('cap.datt_feats', (L, self.opt['att_feat_size']))
-        self.att_embed.dgrad(dadT, L, 1, 1, datt)
-        return datt
+        return self._cap_tail_bwd(dad, att_feats)
 
     # ------------------------------------------------------------------ top-down captioner (ATT:60-101,370-395,486-490; CRIT:43-53)
     # Two nn.LSTMCell per token: att_lstm([h_lang(i-1); fc; xt_i]) -> attention(h_att(i)) -> lang_lstm([att_res; h_att(i)]); the output is
-    # h_lang(i).  Per-token launches only (csrc/topdown_step.hip), 5 forward and 5 backward.  States live in (S+1)-row arrays whose row 0 stays
+    # h_lang(i).  Per-token launches only (csrc/caption_step.hip), 5 forward and 5 backward.  States live in (S+1)-row arrays whose row 0 stays
     # zero: hl / cl / ca row i+1 = step i; `lin` row i+1 = [att_res(i) | h_att(i)], the language cell's input AND the attention cell's state.
     def _topdown_pre(self, d):
         """token-only part: dropout masks, word embedding, the xt columns of att_lstm.weight_ih for all S tokens, the zeroed backward buffer"""
@@ -522,17 +540,9 @@ class resnetv1(Network):
         P, t, S = self.P, self.t, d['S']
         pre = getattr(self, '_cap_pre', None) or self._topdown_pre(d)
         R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
-        V1, FC, Ka = self.opt['vocab_size'] + 1, self.opt['fc_feat_size'], IE + 2 * R
+        FC, Ka = self.opt['fc_feat_size'], IE + 2 * R
         pv = lambda k: P.view('caption_model.' + k)
-        a = self.buf('cap.a', (L, R), f32)
-        self.att_embed.fwd(att_feats, L, 1, 1, a, relu=True, out_f32=True)
-        t['cap.a_pre'], t['cap.drop_att'] = a, pre['drop_att']
-        if pre['drop_att'] is not None:
-            ad = self.buf('cap.ad', (L, R), f32); O.mul(a, pre['drop_att'], ad)
-        else:
-            ad = a
-        patt = self.buf('cap.patt', (L, AH), f32)
-        O.linear_fwd(ad, pv('ctx2att.weight'), pv('ctx2att.bias'), patt, L, AH, R)
+        ad, patt = self._cap_head_fwd(pre, att_feats)
         # fc_embed = Linear + ReLU + dropout on the pooled [mean | masked mean] vector, then its columns of att_lstm.weight_ih (+ bias_hh): once
         fc = t['fc_feats']
         if fc.dtype != f32:
@@ -561,34 +571,21 @@ class resnetv1(Network):
             O.cap_att_dots_fwd(patt, B['att_h'][i], aw, ab, L, AH, B['tanh'][i], B['dots'][i])
             O.cap_att_apply_fwd(ad, B['dots'][i], L, R, B['wgt'][i], lin[i + 1])
             O.topdown_cell_fwd(None, bl_ih, bl_hh, [(lin[i + 1], wl_ih, 2 * R, 2 * R), (hl[i], wl_hh, R, R)], cl[i], cl[i + 1], hl[i + 1], B['act_l'][i], R)
-        t['cap.drop_out'] = pre['drop_out']
-        if pre['drop_out'] is not None:
-            ho = self.buf('cap.ho', (S, R), f32); O.mul(hl[1:], pre['drop_out'], ho)
-        else:
-            ho = hl[1:]
-        logits = self.buf('cap.logits', (S, V1), f32)
-        O.linear_fwd(ho, pv('logit.weight'), pv('logit.bias'), logits, S, V1, R)
-        dlogits = self.buf('cap.dlogits', (S, V1), f32)
-        lp = self.buf('cap.logp', (S, V1), f32) if self.keep_logprobs else None
-        O.logsoftmax_nll(logits, d['cap_tgt'], d['cap_mask'], S, V1, self._cap_loss_weight, loss[5:6], dlogits, lp)
-        t.update({'cap.ad': ad, 'cap.patt': patt, 'cap.xt': pre['xt'], 'cap.drop_xt': pre['drop_xt'], 'cap.ho': ho, 'cap.dlogits': dlogits, 'cap.logp': lp,
-                  'td.fc32': fc32, 'td.fce': fce, 'td.fcd': fcd, 'td.drop_fc': pre['drop_fc'], 'td.zeroed': pre.get('zeroed')})
+        self._cap_tail_fwd(d, pre, hl[1:], ad, patt, loss)
+        t.update({'td.fc32': fc32, 'td.fce': fce, 'td.fcd': fcd, 'td.drop_fc': pre['drop_fc'], 'td.zeroed': pre.get('zeroed')})
 
     def _topdown_bwd(self, d, att_feats):
         """returns d(att_feats) in the activation dtype [196][att_feat_size]; d(fc_feats) float [fc_feat_size] is left in self.t['cap.dfc']"""
         P, t, S = self.P, self.t, d['S']
         R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
-        V1, FC, Ka = self.opt['vocab_size'] + 1, self.opt['fc_feat_size'], IE + 2 * R
+        FC, Ka = self.opt['fc_feat_size'], IE + 2 * R
         pv = lambda k: P.view('caption_model.' + k)
         gv = lambda k: P.view('caption_model.' + k, P.grad)
         wT = lambda k: self.wT['caption_model.' + k][0]
         B = self._topdown_bufs(S)
         hl, cl, ca, lin = B['hl'], B['cl'], B['ca'], B['lin']
-        dlogits, ad = t['cap.dlogits'], t['cap.ad']
-        later = self._cap_deferred = []           # parameter gradients nothing downstream reads: issued behind the branch's result
-        later.append(lambda: O.linear_bwd_w(dlogits, t['cap.ho'], gv('logit.weight'), gv('logit.bias'), S, V1, R))
-        dho = self.buf('cap.dho', (S, R), f32)
-        self.bwd_x(dlogits, 'caption_model.logit.weight', dho, S, mul=t['cap.drop_out'])
+        ad = t['cap.ad']
+        later, dho = self._cap_head_bwd(S)
         nz = L * AH + L * R + 4 * R
         zb = self.buf('td.bwd_zero', (nz,), f32, zero=not t.get('td.zeroed'))
         dpatt = zb[:L * AH].view(L, AH); dad = zb[L * AH:L * AH + L * R].view(L, R); dgsum = zb[L * AH + L * R:]
@@ -654,12 +651,7 @@ class resnetv1(Network):
             O.linear_bwd_w(dpatt, ad, gv('ctx2att.weight'), None, L, AH, R)
             O.colsum(datt_h, S, AH, AH, gv('ctx2att.bias'))
         later.append(recurrence_grads)
-        dadT = self.buf('cap.dadT', (L, R))
-        O.mask_relu_cast(dad, t['cap.drop_att'], t['cap.a_pre'], dadT)
-        self.att_embed.wgrad(dadT, att_feats, L, 1, 1)
-        datt = self.buf('cap.datt_feats', (L, self.opt['att_feat_size']))
-        self.att_embed.dgrad(dadT, L, 1, 1, datt)
-        t['cap.datt'] = datt
+        datt = t['cap.datt'] = self._cap_tail_bwd(dad, att_feats)
         return datt
 
     # ------------------------------------------------------------------ backbone / RoI-head hooks (overridden by the VGG variant)

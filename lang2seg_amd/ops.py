@@ -483,7 +483,7 @@ def _topdown_segs(arr, segs):
 
 
 def topdown_cell_fwd(pre, add0, add1, segs, c_prev, c, h, act, R):
-    """one nn.LSTMCell step (csrc/topdown_step.hip): gates = pre + add0 + add1 + sum over segs (x[n], w, ld, n) of w[4R][:n] . x, with w a
+    """one nn.LSTMCell step (csrc/caption_step.hip): gates = pre + add0 + add1 + sum over segs (x[n], w, ld, n) of w[4R][:n] . x, with w a
     column block (leading dimension ld) of a wider matrix; writes h, c and act[4R] = i, f, g, o.  Up to two segments; None entries are skipped."""
     a = _lib.TopdownFwd()
     a.pre, a.add0, a.add1, a.c_prev, a.c, a.h, a.act = ptr(pre), ptr(add0), ptr(add1), ptr(c_prev), ptr(c), ptr(h), ptr(act)
@@ -509,7 +509,7 @@ def cap_att_apply_fwd(att, dots, L, R, weight, att_res):
 
 
 def cap_att_bwd_step_centered(dweight, tanh_ws, weight, aw, L, D, ddot, datt_h):
-    """cap_attention_bwd_step2 with the sum over the locations centred on its weighted mean (csrc/topdown_step.hip)"""
+    """cap_attention_bwd_step2 with the sum over the locations centred on its weighted mean (csrc/caption_step.hip)"""
     call('l2s_cap_att_bwd_step_centered', ptr(dweight), ptr(tanh_ws), ptr(weight), ptr(aw), L, D, ptr(ddot), ptr(datt_h), stream())
 
 

@@ -1,4 +1,4 @@
-"""The top-down attention captioner on the device (csrc/topdown_step.hip and nets/resnet_v1.py _topdown_pre / _topdown_fwd / _topdown_bwd)
+"""The top-down attention captioner on the device (csrc/caption_step.hip and nets/resnet_v1.py _topdown_pre / _topdown_fwd / _topdown_bwd)
 against the torch restatement of tests/topdown_util.py, which tests/test_topdown_cpu.py pins to the reference's own model.
 Bounds: the kernel family's (tests/test_kernels_gpu.py rel_err) 1e-5 forward and 1e-4 gradients; 1e-4 on losses in exact-f32 mode; bf16:
 losses within 1e-2 and cosine >= 0.99 per gradient tensor against the f32 device step.
@@ -363,19 +363,31 @@ PARENT_LOSSES = {'cycle': '0x1.0cd304p-1 0x1.65a62p-6 0x1.2b53a4p+2 0x1.fb1ba2p-
 PARENT_KEEP = {'cycle': (476, '614f46d67bcc0f576f7b976055252fdfa02abd16'), 'vgg': (239, '9fe81a2b049a71f764701e03878e24d058bc60f3')}
 
 
-def default_step_record(variant, keep):
+def default_step_record(variant, keep, opt_over=None, net_over=None):
     """the tiny default step of __graft_entry__.smoke() (att2in2; production RNG from the device counter, as the tape needs) recorded on a
-    launch tape -> (launches, sha1 of the gradient buffer, losses)"""
+    launch tape -> (launches, sha1 of the gradient buffer, losses).  opt_over: options that differ from the default (an encoder or a
+    captioner other than the default takes its weights from a seeded torch module, as the suites of those paths do); net_over: Network
+    attributes set before the step (cap_persistent, cap_projected)"""
     from lang2seg_amd import selftest, ops as O
     from lang2seg_amd.optim import SGD
     from oracle import weights as OW, synth as OS
+    import rnn_encoder_util
     opt = OW.default_opt(vocab_size=60, seq_length=6)
     if variant == 'vgg':
         opt['C4_feat_dim'] = 512
-    sd = OW.make_state_dict(opt, seed=3, head_gain=4.0, variant=variant)
+    opt.update(opt_over or {})
+    if opt.get('caption_model') == 'topdown':
+        sd = make_sd(opt, seed=3, variant=variant)
+    elif 'rnn_type' in (opt_over or {}):
+        sd = rnn_encoder_util.make_sd(opt, seed=3, variant=variant)
+    else:
+        sd = OW.make_state_dict(opt, seed=3, head_gain=4.0, variant=variant)
     blob = OS.make_blob(160, 224, 6, 60, seed=5)
     over = dict(BATCH_SIZE=16, RPN_PRE_NMS_TOP_N=600, RPN_POST_NMS_TOP_N=100, RPN_BATCHSIZE=64)
     net = selftest.build_net(opt, over, 'f32', sd, variant=variant)
+    for k, v in (net_over or {}).items():
+        assert hasattr(net, k), k
+        setattr(net, k, v)
     net.use_tape = True
     lv = np.asarray(net.train_step(dict(blob), 0, SGD(net, 0.0, keep_grad=True) if keep else SGD(net, 1e-4)), dtype=np.float32)
     torch.cuda.synchronize()
@@ -400,6 +412,45 @@ def test_default_captioner_computes_the_parents_bits(variant):
     n, sha, _ = default_step_record(variant, keep=True)
     print('default step %s, gradients kept: %d launches, grad sha1 %s' % (variant, n, sha))
     assert (n, sha) == PARENT_KEEP[variant]
+
+
+# every other recurrent path (cycle network), recorded in the same way, twice per configuration with equal results, before the step kernels
+# were gathered over csrc/recur.h: name -> (option overrides, Network attribute overrides), and (launches, SHA-1, losses) with the gradients kept
+RECURRENT_PATHS = {
+    'per_token': ({}, dict(cap_persistent=False)),
+    'unprojected': ({}, dict(cap_persistent=False, cap_projected=False)),
+    'topdown': (dict(caption_model='topdown'), {}),
+    'gru2_bi': (dict(rnn_type='gru', rnn_num_layers=2, bidirectional=1), {}),
+    'rnn1_uni': (dict(rnn_type='rnn', rnn_num_layers=1, bidirectional=0), {}),
+    'lstm2_uni': (dict(rnn_type='lstm', rnn_num_layers=2, bidirectional=0), {}),
+}
+PARENT_PATHS = {
+    'gru2_bi': (502, '7de52a4f54feac7f0dc17fff5d85c0165ccf1fbe',
+        '0x1.64136cp+0 0x1.7c9a62p-5 0x1.3645b6p+2 0x1.5d2148p-12 0x1.6f365p-1 0x1.1b4324p+2 0x1.6db994p+3'),
+    'lstm2_uni': (492, '480aefbd69b27ca8ac0ad300543553929af9e345',
+        '0x1.71fed2p-1 0x1.42c196p-6 0x1.31ca16p+2 0x1.47c584p-13 0x1.4d8054p-1 0x1.19492ap+2 0x1.52243cp+3'),
+    'per_token': (516, '122a8af3bcc3ba05dd47ea7f16350be7eaa9030f',
+        '0x1.0cd304p-1 0x1.65a62p-6 0x1.2b53a4p+2 0x1.fb1ba2p-13 0x1.55aef6p-1 0x1.18fe2p+2 0x1.4905dp+3'),
+    'rnn1_uni': (468, '83ea4f5279396975d2ed4a6564c17c9515a2b6b2',
+        '0x1.7d759p+1 0x1.327b74p-2 0x1.215cdcp+2 0x1.3f26fcp-8 0x1.2651aap+0 0x1.143d2p+2 0x1.a8b058p+3'),
+    'topdown': (563, 'ba6d290d178b164bcbe0e106635f2fdd10fe2e7b',
+        '0x1.0cd304p-1 0x1.65a62p-6 0x1.2b53a4p+2 0x1.fb1ba2p-13 0x1.55aef6p-1 0x1.06d3c6p+2 0x1.3ff0a2p+3'),
+    'unprojected': (526, 'bab2ec9385ce1d0f9b38bf9ae7f5ac398bdfb6f8',
+        '0x1.0cd304p-1 0x1.65a62p-6 0x1.2b53a4p+2 0x1.fb1ba2p-13 0x1.55aef6p-1 0x1.18fe2p+2 0x1.4905dp+3'),
+}
+
+
+@pytest.mark.parametrize('name', sorted(RECURRENT_PATHS))
+def test_recurrent_paths_compute_the_parents_bits(name):
+    """the per-token att2in2 kernels (projected and unprojected), the top-down captioner and the GRU / tanh-RNN / stacked LSTM encoders:
+    launches, the SHA-1 of the whole gradient buffer and the losses (to 1e-6) of the tiny step are the parent commit's"""
+    opt_over, net_over = RECURRENT_PATHS[name]
+    n, sha, lv = default_step_record('cycle', True, opt_over, net_over)
+    print('%s: %d launches, grad sha1 %s, losses %s' % (name, n, sha, ' '.join(float(v).hex() for v in lv)))
+    pn, psha, plosses = PARENT_PATHS[name]
+    assert (n, sha) == (pn, psha)
+    ref = np.array([float.fromhex(v) for v in plosses.split()], dtype=np.float32)
+    assert np.allclose(lv, ref, rtol=1e-6, atol=0), (lv, ref)
 
 
 # ------------------------------------------------------------------ 6. strict load

@@ -270,7 +270,7 @@ def test_train_step_vs_fixture_and_oracle(tag, dtype):
 
 
 def test_train_step_per_token_captioner_fallback():
-    """The three-launches-per-token form of the captioner recurrence (lang.hip) is what a network whose shapes the resident launches do not take
+    """The three-launches-per-token form of the captioner recurrence (caption_step.hip) is what a network whose shapes the resident launches do not take
     (rnn_size / att_hid_size != 512, > 224 attention locations) falls back to; every fixture has the resident shapes, so the fallback is run
     here explicitly (Network.cap_persistent = False) on the tiny cycle fixture: same losses and caption-side gradients as the reference run, and
     within fp32 rounding of the resident form."""
