@@ -23,6 +23,8 @@ ARGS="--imdb_name ${IMDB} --net_name ${NET} --iters ${ITERS} --tag ${TAG} --data
   --output_postfix ${OUTPUT_POSTFIX} --caption_model ${CAPTION_MODEL} --start_from caption_log_res5_2 \
   --cap_loss_weight ${CAPTION_LOSS_WEIGHT} --max_iters ${MAX_ITERS:-800000} --with_st 1 --id ${ID} \
   --cfg experiments/cfgs/${NET}.yml --set ANCHOR_SCALES ${ANCHORS} ANCHOR_RATIOS ${RATIOS} TRAIN.STEPSIZE ${STEPSIZE}"
+# the adaptive-attention captioners are opt-in (tools/opt.py --adaatt)
+case "${CAPTION_MODEL}" in adaatt|adaattmo) ARGS="${ARGS} --adaatt 1";; esac
 if [ "${NGPU}" -gt 1 ]; then
   HIP_VISIBLE_DEVICES=${GPU_ID} python -m torch.distributed.run --nnodes=1 --nproc-per-node ${NGPU} --master-addr 127.0.0.1 \
     --master-port ${MASTER_PORT:-29511} ./tools/train_cycle_2.py ${ARGS}

@@ -405,6 +405,32 @@ int l2s_cap_att_bwd_step_centered(const float* dweight, const float* tanh_ws, co
                                   float* datt_h, hipStream_t s);
 /* dst[r][0..cols) = src[r][0..cols) with leading dimensions ldd / lds; lds = 0 repeats one source row */
 int l2s_pack_rows(float* dst, int ldd, const float* src, int lds, int rows, int cols, hipStream_t s);
+/* Adaptive-attention captioners (csrc/adaatt_step.hip; AttModel.py:211-368).  G = 4 (adaatt) or 5 (adaattmo: two transform rows, their max).
+ * Cell, one token: sums[q R + j] = pre + fcrow + w_hh[q R + j] . h_prev + b_hh (q < G; row blocks in, forget, out, transform) and
+ * n5[j] = pre[G R + j] + fcrow[G R + j] + w_r[j] . h_prev + b_r[j]; pre / fcrow are [(G+1) R].  Writes c, h, fake = sigmoid(n5) tanh(c) and
+ * save[7 R] (in, forget, out, transform, selector, tanh(c), sigmoid(n5)).
+ * backward: dh = dh_ext + t_hh[j] . dsn[0 .. G R) + t_r[j] . dsn[G R ..) with t_hh [R][ld_thh] / t_r [R][ld_tr] transposed copies and dsn the
+ * ds of token i + 1 (NULL at the last token); writes ds[(G+1) R] = d(sums | n5) and dc_prev.  dfake / dc_in / dh_ext may be NULL.
+ * R % 4 != 0, R < 4, G not 4 or 5, a leading dimension shorter than its rows: error code, nothing launched. */
+typedef struct { const float* pre; const float* fcrow; const float* w_hh; const float* b_hh; const float* w_r; const float* b_r; int ld_hh; int ld_r;
+                 const float* h_prev; const float* c_prev; float* c; float* h; float* fake; float* save; } l2s_adaatt_fwd;
+typedef struct { const float* dsn; const float* t_hh; const float* t_r; int ld_thh; int ld_tr; const float* dh_ext; const float* dfake;
+                 const float* dc_in; const float* save; const float* c_prev; float* ds; float* dc_prev; } l2s_adaatt_bwd;
+int l2s_adaatt_cell_fwd(const l2s_adaatt_fwd* a, int R, int G, hipStream_t s);
+int l2s_adaatt_cell_bwd(const l2s_adaatt_bwd* a, int R, int G, hipStream_t s);
+/* Attention over L + 1 slots for S tokens at once (it does not feed the recurrence): slot 0 is the token's sentinel (frl[s], embedded fre[s]),
+ * slots 1..L the locations (att [L][R], patt [L][R]).  tanh_ws[S][L+1][R] = tanh(embed_slot + hoe[s]) (before `mask`, the hA dropout mask
+ * [S][L+1][R] or NULL), dots [S][256], PI[S][L+1] = softmax, atten[S][R] = PI[0] frl + sum_l PI[l] att[l-1] + hol.  L + 1 <= 256. */
+int l2s_adaatt_att_fwd(const float* att, const float* patt, const float* frl, const float* fre, const float* hoe, const float* hol, const float* aw,
+                       const float* ab, const float* mask, int S, int L, int R, float* tanh_ws, float* dots, float* PI, float* atten, hipStream_t s);
+/* its backward per token, what flows on to the cell: ddot[S][L+1] (softmax backward), dhoe / dfre [S][R] (the sum over the slots taken about
+ * its PI-weighted mean), dctx = dhoe - dfre, dfrl = PI[0] datten, dhol = datten.  R % 4 == 0, 16-byte aligned datten / att / frl. */
+int l2s_adaatt_att_bwd_step(const float* datten, const float* att, const float* frl, const float* tanh_ws, const float* mask, const float* PI,
+                            const float* aw, int S, int L, int R, float* ddot, float* dhoe, float* dfre, float* dctx, float* dfrl, float* dhol,
+                            hipStream_t s);
+/* and what is summed over the tokens: dpatt[L][R] +=, datt[L][R] += sum_s PI[s][l] datten[s], daw[R] += (all slots) */
+int l2s_adaatt_att_bwd_batched(const float* ddot, const float* PI, const float* datten, const float* tanh_ws, const float* mask, const float* aw,
+                               int S, int L, int R, float* dpatt, float* datt, float* daw, hipStream_t s);
 /* dynamic-filter correlation (NET:504-562): filt float [7][C] (tanh'ed), r float [7].
  * y(dtype)[HW][C] = x * resp, resp float [HW], respk float [HW][7] (masked per-filter responses) */
 int l2s_dynfilter_fwd(const void* x, const float* filt, const float* r, void* y, float* resp, float* respk, int H, int W, int C,

@@ -80,6 +80,16 @@ class TopdownBwd(C.Structure):
                 ('dc_prev', vp)]
 
 
+class AdaattFwd(C.Structure):
+    _fields_ = [(n, vp) for n in ('pre', 'fcrow', 'w_hh', 'b_hh', 'w_r', 'b_r')] + [('ld_hh', i32), ('ld_r', i32)] + \
+               [(n, vp) for n in ('h_prev', 'c_prev', 'c', 'h', 'fake', 'save')]
+
+
+class AdaattBwd(C.Structure):
+    _fields_ = [(n, vp) for n in ('dsn', 't_hh', 't_r')] + [('ld_thh', i32), ('ld_tr', i32)] + \
+               [(n, vp) for n in ('dh_ext', 'dfake', 'dc_in', 'save', 'c_prev', 'ds', 'dc_prev')]
+
+
 class Bottleneck64Desc(C.Structure):
     _fields_ = [(n, vp) for n in ('a', 'x', 'w2', 'w3', 'wd', 'w1n', 'b2', 'b3', 'bd', 'b1n', 'y', 'a_next')] + [(n, i32) for n in ('H', 'W', 'Cx')]
 
@@ -206,6 +216,11 @@ SIGS = {
     'l2s_cap_att_apply_fwd': (i32, [vp, vp, i32, i32, vp, vp, vp]),
     'l2s_cap_att_bwd_step_centered': (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp]),
     'l2s_pack_rows': (i32, [vp, i32, vp, i32, i32, i32, vp]),
+    'l2s_adaatt_cell_fwd': (i32, [C.POINTER(AdaattFwd), i32, i32, vp]),
+    'l2s_adaatt_cell_bwd': (i32, [C.POINTER(AdaattBwd), i32, i32, vp]),
+    'l2s_adaatt_att_fwd': (i32, [vp] * 9 + [i32, i32, i32] + [vp] * 5),
+    'l2s_adaatt_att_bwd_step': (i32, [vp] * 7 + [i32, i32, i32] + [vp] * 7),
+    'l2s_adaatt_att_bwd_batched': (i32, [vp] * 6 + [i32, i32, i32] + [vp] * 4),
     'l2s_rcnn_predict': (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     'l2s_mask_prob': (i32, [vp, i32, i32, vp, i32, C.c_long, vp, vp]),
     'l2s_response_loss': (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]),

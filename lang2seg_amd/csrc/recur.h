@@ -1,5 +1,6 @@
 // Device functions shared by the recurrent step kernels (rnn_step.hip, caption_step.hip, cap_recur.hip; lang.hip takes sigm): the scalar
-// pieces, the LSTM cell and the att2in2 gate block with their backward passes, and the workgroup-wide softmax of the attention kernels.
+// pieces, the LSTM cell, the att2in2 gate block and the adaptive-attention cell (adaatt_step.hip) with their backward passes, and the
+// workgroup-wide softmax of the attention kernels.
 // Every function works on values in registers: the kernel loads the operands and stores the results where its layout wants them.  The
 // expressions are the ones the kernels carried inline; the step's gradient bits are pinned by tests/test_topdown_gpu.py.
 #pragma once
@@ -76,6 +77,38 @@ __device__ __forceinline__ void att2in_gates_bwd(const float save[6], float dhj,
   ds[2] = dhj * tc * og * (1.f - og);
   const float dit = dcn * ig;
   d0 = sel == 0.f ? dit : 0.f; d1 = sel == 0.f ? 0.f : dit;
+  dc_prev = dcn * fg;
+}
+
+// ---- the adaptive-attention cell (ATT:258-285), row blocks in, forget, out, transform: NOT nn.LSTM's order.  MAXOUT (adaattmo): two transform
+// rows and their max without a tanh (torch.max(a, b): first wins ties, as above); otherwise tanh of the one row.  n5: the sentinel gate's sum.
+// save: in gate, forget gate, out gate, transform, selector of the max, tanh(c), sigmoid(n5)
+template <bool MAXOUT>
+__device__ __forceinline__ void adaatt_cell_fwd(const float* s, float n5, float c_prev, float& c, float& h, float& fake, float save[7]) {
+  const float ig = sigm(s[0]), fg = sigm(s[1]), og = sigm(s[2]);
+  float it, sel = 0.f;
+  if (MAXOUT) { it = fmaxf(s[3], s[4]); sel = (s[3] >= s[4]) ? 0.f : 1.f; }
+  else it = tanhf(s[3]);
+  const float cn = fg * c_prev + ig * it;
+  const float tc = tanhf(cn);
+  const float sg = sigm(n5);
+  c = cn; h = og * tc; fake = sg * tc;
+  save[0] = ig; save[1] = fg; save[2] = og; save[3] = it; save[4] = sel; save[5] = tc; save[6] = sg;
+}
+// dh: recurrent part + d(top_h); dfake: d(fake).  tanh(c) feeds both h and the sentinel.  ds: gradients of the four (five) sums; dn5: of n5
+template <bool MAXOUT>
+__device__ __forceinline__ void adaatt_cell_bwd(const float save[7], float dh, float dfake, float dc_in, float c_prev, float ds[5], float& dn5,
+                                                float& dc_prev) {
+  const float ig = save[0], fg = save[1], og = save[2], it = save[3], sel = save[4], tc = save[5], sg = save[6];
+  const float dtc = og * dh + sg * dfake;
+  const float dcn = dc_in + dtc * (1.f - tc * tc);
+  ds[0] = dcn * it * ig * (1.f - ig);
+  ds[1] = dcn * c_prev * fg * (1.f - fg);
+  ds[2] = dh * tc * og * (1.f - og);
+  const float dit = dcn * ig;
+  if (MAXOUT) { ds[3] = sel == 0.f ? dit : 0.f; ds[4] = sel == 0.f ? 0.f : dit; }
+  else { ds[3] = dit * (1.f - it * it); ds[4] = 0.f; }
+  dn5 = dfake * tc * sg * (1.f - sg);
   dc_prev = dcn * fg;
 }
 

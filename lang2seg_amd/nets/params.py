@@ -76,33 +76,54 @@ def encoder_rnn_shapes(opt):
     return s
 
 
-CAPTIONERS = ('att2in2', 'topdown')             # caption_models.setup(opt) names seven more; these two are built
-# a tensor only one of the captioners has: tells whose keys a state dict holds
-CAPTIONER_MARK = {'att2in2': 'core.i2h.weight', 'topdown': 'core.att_lstm.weight_ih'}
+CAPTIONERS = ('att2in2', 'topdown', 'adaatt', 'adaattmo')     # caption_models.setup(opt) names five more; these four are built (the AdaAtt pair with --adaatt 1)
+# a tensor only one of the captioners has: tells whose keys a state dict holds.  (adaatt / adaattmo share every key and differ in the row
+# count of w2h / v2h / h2h.0 - 4 or 5 rnn_size: check_caption_keys tells them apart by shape.)
+CAPTIONER_MARK = {'att2in2': 'core.i2h.weight', 'topdown': 'core.att_lstm.weight_ih', 'adaatt': 'core.lstm.w2h.weight',
+                  'adaattmo': 'core.lstm.w2h.weight'}
+ADAATT_GATES = {'adaatt': 4, 'adaattmo': 5}       # row blocks of w2h / v2h / h2h.0: in, forget, out, transform (adaattmo: two, their max)
+FC_CAPTIONERS = ('topdown', 'adaatt', 'adaattmo')  # the captioners that read fc_feats (Att2in2Model deletes fc_embed)
 
 
 def caption_config(opt):
     """the captioner `--caption_model` names (caption_models/__init__.py:17-43); ValueError names the option it rejects"""
     m = str(opt.get('caption_model', 'att2in2'))
-    if m not in CAPTIONERS:
-        raise ValueError('--caption_model %r: the caption branch has %s' % (opt.get('caption_model'), ' and '.join(repr(c) for c in CAPTIONERS)))
-    if m == 'topdown' and (int(opt['rnn_size']) % 4 or int(opt['rnn_size']) < 4):
-        raise ValueError('rnn_size %r: the recurrent kernels of --caption_model topdown need a multiple of 4' % (opt['rnn_size'],))
+    # the AdaAtt pair is opt-in (--adaatt 1): a bare `--caption_model adaatt` stays the error it was, so nothing that relied on it changes
+    if m not in CAPTIONERS or (m in ADAATT_GATES and not int(opt.get('adaatt') or 0)):
+        raise ValueError("--caption_model %r: the caption branch has 'att2in2' and 'topdown', and with --adaatt 1 'adaatt' and 'adaattmo'"
+                         % (opt.get('caption_model'),))
+    if m != 'att2in2' and (int(opt['rnn_size']) % 4 or int(opt['rnn_size']) < 4):
+        raise ValueError('rnn_size %r: the recurrent kernels of --caption_model %s need a multiple of 4' % (opt['rnn_size'], m))
+    if m in ADAATT_GATES:
+        # ATT:341-342 view the sentinel (input_encoding_size wide) and its embedding (att_hid_size wide) beside the rnn_size-wide features
+        if not (int(opt['input_encoding_size']) == int(opt['rnn_size']) == int(opt['att_hid_size'])):
+            raise ValueError('--caption_model %s needs input_encoding_size == rnn_size == att_hid_size (%r, %r, %r): the reference concatenates '
+                             'the sentinel with the attention features' % (m, opt['input_encoding_size'], opt['rnn_size'], opt['att_hid_size']))
+        if int(opt.get('num_layers', 1)) != 1:
+            raise ValueError('--num_layers %r with --caption_model %s: the stacked AdaAtt cell (i2h, r_i2h, inter-layer dropout) is not built'
+                             % (opt.get('num_layers'), m))
     return m
 
 
 def caption_shapes(opt):
     """torch's own keys and shapes of the captioner's state_dict() under 'caption_model.', in torch's order (ATT:27-57; Att2in2Model deletes
-    fc_embed, ATT:479-484; TopDownCore is two nn.LSTMCell, ATT:370-377)"""
+    fc_embed, ATT:479-484; TopDownCore is two nn.LSTMCell, ATT:370-377; AdaAttCore is AdaAtt_lstm + AdaAtt_attention, ATT:211-368)"""
     m = caption_config(opt)
     V, R, IE, AH = opt['vocab_size'], opt['rnn_size'], opt['input_encoding_size'], opt['att_hid_size']
     s = {}
     s['embed.0.weight'] = (V + 1, IE)
-    if m == 'topdown':
+    if m in FC_CAPTIONERS:
         s['fc_embed.0.weight'] = (R, opt['fc_feat_size']); s['fc_embed.0.bias'] = (R,)
     s['att_embed.0.weight'] = (R, opt['att_feat_size']); s['att_embed.0.bias'] = (R,)
     s['logit.weight'] = (V + 1, R); s['logit.bias'] = (V + 1,)
     s['ctx2att.weight'] = (AH, R); s['ctx2att.bias'] = (AH,)
+    if m in ADAATT_GATES:
+        G = ADAATT_GATES[m]
+        for k, N, K in (('lstm.w2h', G * R, IE), ('lstm.v2h', G * R, R), ('lstm.h2h.0', G * R, R), ('lstm.r_w2h', R, IE), ('lstm.r_v2h', R, R),
+                        ('lstm.r_h2h', R, R), ('attention.fr_linear.0', IE, R), ('attention.fr_embed', AH, IE), ('attention.ho_linear.0', IE, R),
+                        ('attention.ho_embed', AH, IE), ('attention.alpha_net', 1, AH), ('attention.att2h', R, R)):
+            s['core.%s.weight' % k] = (N, K); s['core.%s.bias' % k] = (N,)
+        return {'caption_model.' + k: v for k, v in s.items()}
     if m == 'topdown':
         for cell, K in (('att_lstm', IE + 2 * R), ('lang_lstm', 2 * R)):
             s['core.%s.weight_ih' % cell] = (4 * R, K); s['core.%s.weight_hh' % cell] = (4 * R, R)
@@ -116,13 +137,27 @@ def caption_shapes(opt):
     return {'caption_model.' + k: v for k, v in s.items()}
 
 
-def check_caption_keys(opt, keys, prefix='caption_model.'):
-    """`keys` (of a state dict, or of a caption model-best.pth with prefix '') that hold a captioner must hold THIS network's: the other
-    captioner's is an error naming the option to change"""
-    mine = caption_config(opt)
-    for other, mark in CAPTIONER_MARK.items():
-        if other != mine and (prefix + mark) in keys and (prefix + CAPTIONER_MARK[mine]) not in keys:
-            raise ValueError('the state dict holds another captioner; it was trained with --caption_model %s (this network: %s)' % (other, mine))
+def captioner_of(sd, prefix='caption_model.'):
+    """the captioner whose tensors the dict `sd` holds (by marker key; the AdaAtt pair by the rows of h2h.0 per column), or None"""
+    k = prefix + 'core.lstm.h2h.0.weight'
+    if k in sd:
+        shp = tuple(sd[k].shape)
+        for name, G in ADAATT_GATES.items():
+            if len(shp) == 2 and shp[0] == G * shp[1]:
+                return name
+        return 'adaatt'
+    for name, mark in CAPTIONER_MARK.items():
+        if (prefix + mark) in sd:
+            return name
+    return None
+
+
+def check_caption_keys(opt, sd, prefix='caption_model.'):
+    """`sd` (a state dict, or a caption model-best.pth with prefix '') that holds a captioner must hold THIS network's: the other
+    captioner's is an error naming the option to change.  The AdaAtt pair shares every key, so the shape decides, not only a marker key."""
+    mine, theirs = caption_config(opt), captioner_of(sd, prefix)
+    if theirs is not None and theirs != mine:
+        raise ValueError('the state dict holds another captioner; it was trained with --caption_model %s (this network: %s)' % (theirs, mine))
 
 
 class ParamStore(object):

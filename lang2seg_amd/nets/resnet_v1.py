@@ -13,7 +13,7 @@ from .. import ops as O
 from .._lib import F32, BF16
 from ..model.config import cfg
 from .network import Network, ConvOp, Bottleneck
-from .params import ParamStore, encoder_config, caption_config
+from .params import ParamStore, encoder_config, caption_config, ADAATT_GATES, FC_CAPTIONERS
 from .variants import solver_cfg
 from . import anchors as ANC
 
@@ -32,7 +32,7 @@ class resnetv1(Network):
         self._num_layers = num_layers
         self.opt = dict(opt)
         self.enc = encoder_config(self.opt)      # (rnn_type, layers, directions, gate rows per unit); ValueError names a rejected option
-        # the captioner --caption_model names ('att2in2' | 'topdown'; ValueError otherwise); networks without a caption branch ignore the option
+        # the captioner --caption_model names (nets/params.py CAPTIONERS; ValueError otherwise); networks without a caption branch ignore the option
         self.cap_model = caption_config(self.opt) if self.var['cap'] is not None else None
         self._cap_loss_weight = float(self.opt.get('cap_loss_weight', 0.0)) if self.var['cap'] is not None else 0.0   # RES:253
         self._C4_feat_dim = self.opt['C4_feat_dim']
@@ -135,6 +135,8 @@ class resnetv1(Network):
             # both cells' matrices (att_lstm.weight_ih: its h_lang and fc column blocks, rows of the transposed copy) and h2att
             capk = ['caption_model.core.%s' % k for k in ('att_lstm.weight_ih', 'att_lstm.weight_hh', 'lang_lstm.weight_ih', 'lang_lstm.weight_hh',
                                                           'attention.h2att.weight')]
+        elif self.cap_model in ADAATT_GATES:
+            capk = ['caption_model.core.lstm.h2h.0.weight', 'caption_model.core.lstm.r_h2h.weight']     # what token i + 1 reads of h(i)
         else:
             capk = ['caption_model.core.h2h.weight', 'caption_model.core.attention.h2att.weight']
             if not (self.cap_projected and self.opt['rnn_size'] <= 1024):
@@ -386,6 +388,8 @@ class resnetv1(Network):
         """token-only part of _caption_fwd / _caption_bwd, issued early on the language stream"""
         if self.cap_model == 'topdown':
             return self._topdown_pre(d)
+        if self.cap_model in ADAATT_GATES:
+            return self._adaatt_pre(d)
         P, S = self.P, d['S']
         R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
         pv = lambda k: P.view('caption_model.' + k)
@@ -404,6 +408,8 @@ class resnetv1(Network):
     def _caption_fwd(self, d, att_feats, loss):
         if self.cap_model == 'topdown':
             return self._topdown_fwd(d, att_feats, loss)
+        if self.cap_model in ADAATT_GATES:
+            return self._adaatt_fwd(d, att_feats, loss)
         P, t, S = self.P, self.t, d['S']
         pre = getattr(self, '_cap_pre', None) or self._caption_pre(d)
         R, AH, L = self.opt['rnn_size'], self.opt['att_hid_size'], 196
@@ -446,6 +452,8 @@ class resnetv1(Network):
         """returns d(att_feats) in the activation dtype [196][att_feat_size]."""
         if self.cap_model == 'topdown':
             return self._topdown_bwd(d, att_feats)
+        if self.cap_model in ADAATT_GATES:
+            return self._adaatt_bwd(d, att_feats)
         P, t, S = self.P, self.t, d['S']
         R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
         SC = 256
@@ -650,6 +658,105 @@ class resnetv1(Network):
             # well-conditioned form; the column sums of dpatt would add that sum's rounding error back
             O.linear_bwd_w(dpatt, ad, gv('ctx2att.weight'), None, L, AH, R)
             O.colsum(datt_h, S, AH, AH, gv('ctx2att.bias'))
+        later.append(recurrence_grads)
+        datt = t['cap.datt'] = self._cap_tail_bwd(dad, att_feats)
+        return datt
+
+    # ------------------------------------------------------------------ adaptive-attention captioners (ATT:211-368,468-477; adaatt / adaattmo)
+    # An LSTM with a sentinel gate, then an additive attention over the 196 locations + the sentinel.  Only the cell is recurrent: one launch per
+    # token each way; the attention runs once for all tokens (nets/adaatt.py has the sequence, csrc/adaatt_step.hip the kernels).
+    def _adaatt_masks(self, pre):
+        return {k: pre['drop_' + k] for k in ('toph', 'fake', 'frl', 'hol', 'hA')}
+
+    def _adaatt_pre(self, d):
+        """token-only part: dropout masks, word embedding, w2h(xt) | r_w2h(xt) for all S tokens, the zeroed backward buffer"""
+        P, S = self.P, d['S']
+        R, IE, L, G = self.opt['rnn_size'], self.opt['input_encoding_size'], 196, ADAATT_GATES[self.cap_model]
+        pv = lambda k: P.view('caption_model.' + k)
+        p = self.opt['drop_prob_lm']
+        pre = {'drop_att': self._drop('att', (L, R), p), 'drop_fc': self._drop('fc', (R,), p), 'drop_xt': self._drop('xt', (S, IE), p),
+               'drop_out': self._drop('out', (S, R), p), 'drop_hA': self._drop('hA', (S, L + 1, R), p)}
+        for k in ('toph', 'fake', 'frl', 'hol'):
+            pre['drop_' + k] = self._drop(k, (S, R), p)
+        xt = self.buf('cap.xt', (S, IE), f32)
+        O.embed_fwd(pv('embed.0.weight'), d['cap_in'], pre['drop_xt'], xt, S, IE, True)
+        W = (G + 1) * R
+        xpre = self.buf('ada.xpre', (S, W), f32)
+        O.linear_fwd(xt, pv('core.lstm.w2h.weight'), pv('core.lstm.w2h.bias'), xpre, S, G * R, IE, ldy=W)
+        O.linear_fwd(xt, pv('core.lstm.r_w2h.weight'), pv('core.lstm.r_w2h.bias'), xpre[:, G * R:], S, R, IE, ldy=W)
+        self.buf('ada.bwd_zero', (2 * L * R + W,), f32, zero=True)                 # dpatt | dad | sum over tokens of d(sums | n5)
+        pre.update(xt=xt, xpre=xpre, zeroed=True)
+        return pre
+
+    def _adaatt_fwd(self, d, att_feats, loss):
+        from . import adaatt as AA
+        P, t, S = self.P, self.t, d['S']
+        pre = getattr(self, '_cap_pre', None) or self._adaatt_pre(d)
+        R, L, G = self.opt['rnn_size'], 196, ADAATT_GATES[self.cap_model]
+        FC = self.opt['fc_feat_size']
+        pv = lambda k: P.view('caption_model.' + k)
+        ad, patt = self._cap_head_fwd(pre, att_feats)
+        # fc_embed = Linear + ReLU + dropout on the pooled vector, then v2h | r_v2h of it: once per sentence
+        fc = t['fc_feats']
+        if fc.dtype != f32:
+            fc32 = self.buf('ada.fc32', (FC,), f32); O.cast(fc, fc32)
+        else:
+            fc32 = fc
+        fce = self.buf('ada.fce', (R,), f32)
+        O.linear_fwd(fc32, pv('fc_embed.0.weight'), pv('fc_embed.0.bias'), fce, 1, R, FC, act=1)
+        if pre['drop_fc'] is not None:
+            fcd = self.buf('ada.fcd', (R,), f32); O.mul(fce, pre['drop_fc'], fcd)
+        else:
+            fcd = fce
+        fcrow = self.buf('ada.fcrow', ((G + 1) * R,), f32)
+        O.linear_fwd(fcd, pv('core.lstm.v2h.weight'), pv('core.lstm.v2h.bias'), fcrow, 1, G * R, R)
+        O.linear_fwd(fcd, pv('core.lstm.r_v2h.weight'), pv('core.lstm.r_v2h.bias'), fcrow[G * R:], 1, R, R)
+        B = {k: self.buf('ada.' + k, shp, f32) for k, shp in AA.fwd_shapes(S, L, R).items()}
+        V = AA.core_fwd(O, lambda k: pv('core.' + k), B, pre['xpre'], fcrow, ad, patt, self._adaatt_masks(pre), S, L, R, G)
+        self._cap_tail_fwd(d, pre, B['outs'], ad, patt, loss)
+        t.update({'ada.fc32': fc32, 'ada.fce': fce, 'ada.fcd': fcd, 'ada.pre': pre, 'ada.B': B, 'ada.V': V, 'ada.zeroed': pre.get('zeroed')})
+
+    def _adaatt_bwd(self, d, att_feats):
+        """returns d(att_feats) in the activation dtype [196][att_feat_size]; d(fc_feats) float [fc_feat_size] is left in self.t['cap.dfc']"""
+        from . import adaatt as AA
+        P, t, S = self.P, self.t, d['S']
+        R, IE, L, G = self.opt['rnn_size'], self.opt['input_encoding_size'], 196, ADAATT_GATES[self.cap_model]
+        FC, W = self.opt['fc_feat_size'], (G + 1) * R
+        pv = lambda k: P.view('caption_model.core.' + k)
+        gv = lambda k: P.view('caption_model.' + k, P.grad)
+        B, V, masks = t['ada.B'], t['ada.V'], self._adaatt_masks(t['ada.pre'])
+        ad = t['cap.ad']
+        later, dho = self._cap_head_bwd(S)
+        zb = self.buf('ada.bwd_zero', (2 * L * R + W,), f32, zero=not t.get('ada.zeroed'))
+        dpatt = zb[:L * R].view(L, R); dad = zb[L * R:2 * L * R].view(L, R); dgsum = zb[2 * L * R:]
+        D = {k: self.buf('ada.' + k, shp, f32) for k, shp in AA.bwd_shapes(S, L, R, G).items()}
+        wT = (self.wT['caption_model.core.lstm.h2h.0.weight'][0], self.wT['caption_model.core.lstm.r_h2h.weight'][0])
+        bwd_x = lambda dy, k, dx, M, **kw: self.bwd_x(dy, 'caption_model.core.' + k, dx, M, **kw)
+        AA.core_bwd(O, pv, wT, bwd_x, B, D, V, dho, ad, dpatt, dad, gv('core.attention.alpha_net.weight'), masks, S, L, R, G)
+        # d(fc_feats): v2h | r_v2h see every token's gradient, so their sum goes through the two matrices once
+        O.colsum(D['dall'], S, W, W, dgsum)
+        dfcd = self.buf('ada.dfcd', (R,), f32)
+        bwd_x(dgsum, 'lstm.v2h.weight', dfcd, 1)
+        bwd_x(dgsum[G * R:], 'lstm.r_v2h.weight', dfcd, 1, accumulate=True)
+        if t['ada.pre']['drop_fc'] is not None:
+            O.mul(dfcd, t['ada.pre']['drop_fc'], dfcd)
+        O.act_bwd(dfcd, t['ada.fce'], 1)
+        dfc = self.buf('ada.dfc', (FC,), f32)
+        self.bwd_x(dfcd, 'caption_model.fc_embed.0.weight', dfc, 1)
+        t['cap.dfc'] = dfc
+        self.bwd_x(dpatt, 'caption_model.ctx2att.weight', dad, L, accumulate=True)
+
+        def recurrence_grads():
+            AA.core_wgrads(O, lambda k: gv('core.' + k), B, D, V, dho, t['cap.xt'], t['ada.fcd'], dgsum, S, R, IE, G)
+            O.linear_bwd_w(dfcd, t['ada.fc32'], gv('fc_embed.0.weight'), gv('fc_embed.0.bias'), 1, R, FC)
+            dxt = self.buf('cap.dxt', (S, IE), f32)
+            bwd_x(D['dall'], 'lstm.w2h.weight', dxt, S, lddy=W)
+            bwd_x(D['dall'][:, G * R:], 'lstm.r_w2h.weight', dxt, S, accumulate=True, lddy=W)
+            O.embed_bwd(dxt, t['cap.xt'], d['cap_in'], t['cap.drop_xt'], gv('embed.0.weight'), S, IE, True)
+            # ctx2att.bias: the sum over the LOCATIONS of what enters the tanh, taken in the well-conditioned form by the step kernel (dctx);
+            # the column sums of dpatt would add that sum's rounding error back (as for the top-down captioner)
+            O.linear_bwd_w(dpatt, ad, gv('ctx2att.weight'), None, L, R, R)
+            O.colsum(D['dctx'], S, R, R, gv('ctx2att.bias'))
         later.append(recurrence_grads)
         datt = t['cap.datt'] = self._cap_tail_bwd(dad, att_feats)
         return datt
@@ -1065,7 +1172,7 @@ class resnetv1(Network):
             feats = l4_on_map(net_conv, 'l4m')
             self._mark('cap: layer4 on map fwd')
             att = self.buf('cap.att', (196, AF))
-            topdown = self.cap_model == 'topdown'
+            topdown = self.cap_model in FC_CAPTIONERS        # the captioner reads fc_feats (top-down and the AdaAtt pair)
             if topdown:
                 FC = self.opt['fc_feat_size']
                 if FC != 2 * 2048:
@@ -1113,7 +1220,7 @@ class resnetv1(Network):
             g = self.buf('l4m.g', (HW, 2048))
 
             def fc_grad():
-                """d(fc_feats) of the top-down captioner in the activation dtype"""
+                """d(fc_feats) of a captioner that reads them, in the activation dtype"""
                 dfc32 = t['cap.dfc']
                 if self.dt == F32:
                     return dfc32

@@ -518,6 +518,43 @@ def pack_rows(dst, ldd, src, lds, rows, cols):
     call('l2s_pack_rows', ptr(dst), int(ldd), ptr(src), int(lds), int(rows), int(cols), stream())
 
 
+def adaatt_cell_fwd(pre, fcrow, w_hh, b_hh, w_r, b_r, h_prev, c_prev, c, h, fake, save, R, G, ld_hh=None, ld_r=None):
+    """one token of the adaptive-attention cell (csrc/adaatt_step.hip): sums = pre + fcrow + w_hh h_prev + b_hh (G row blocks: in, forget, out,
+    transform; G = 5: the max of two transforms), n5 = the row after them + w_r h_prev + b_r; writes c, h, fake = sigmoid(n5) tanh(c), save[7R]"""
+    a = _lib.AdaattFwd()
+    a.pre, a.fcrow, a.w_hh, a.b_hh, a.w_r, a.b_r = ptr(pre), ptr(fcrow), ptr(w_hh), ptr(b_hh), ptr(w_r), ptr(b_r)
+    a.ld_hh, a.ld_r = int(R if ld_hh is None else ld_hh), int(R if ld_r is None else ld_r)
+    a.h_prev, a.c_prev, a.c, a.h, a.fake, a.save = ptr(h_prev), ptr(c_prev), ptr(c), ptr(h), ptr(fake), ptr(save)
+    call('l2s_adaatt_cell_fwd', C.byref(a), int(R), int(G), stream())
+
+
+def adaatt_cell_bwd(dsn, t_hh, t_r, dh_ext, dfake, dc_in, save, c_prev, ds, dc_prev, R, G, ld_thh=None, ld_tr=None):
+    """its backward: dh = dh_ext + the unit's rows of the transposed copies t_hh [R][G R] / t_r [R][R] with dsn = d(sums | n5) of the next token
+    (None at the last); writes ds[(G+1) R] = d(sums | n5) and dc_prev"""
+    a = _lib.AdaattBwd()
+    a.dsn, a.t_hh, a.t_r, a.ld_thh, a.ld_tr = ptr(dsn), ptr(t_hh), ptr(t_r), int(G * R if ld_thh is None else ld_thh), int(R if ld_tr is None else ld_tr)
+    a.dh_ext, a.dfake, a.dc_in, a.save, a.c_prev, a.ds, a.dc_prev = ptr(dh_ext), ptr(dfake), ptr(dc_in), ptr(save), ptr(c_prev), ptr(ds), ptr(dc_prev)
+    call('l2s_adaatt_cell_bwd', C.byref(a), int(R), int(G), stream())
+
+
+def adaatt_att_fwd(att, patt, frl, fre, hoe, hol, aw, ab, mask, S, L, R, tanh_ws, dots, PI, atten):
+    """the attention over L + 1 slots (slot 0 = sentinel) for S tokens: tanh_ws[S][L+1][R], dots[S][256], PI[S][L+1], atten[S][R]"""
+    call('l2s_adaatt_att_fwd', ptr(att), ptr(patt), ptr(frl), ptr(fre), ptr(hoe), ptr(hol), ptr(aw), ptr(ab), ptr(mask), int(S), int(L), int(R),
+         ptr(tanh_ws), ptr(dots), ptr(PI), ptr(atten), stream())
+
+
+def adaatt_att_bwd_step(datten, att, frl, tanh_ws, mask, PI, aw, S, L, R, ddot, dhoe, dfre, dctx, dfrl, dhol):
+    """what flows from d(atten)[S][R] on to the cell: ddot[S][L+1], d(hoe), d(fre), dctx = d(hoe) - d(fre), d(frl) = PI[0] datten, d(hol) = datten"""
+    call('l2s_adaatt_att_bwd_step', ptr(datten), ptr(att), ptr(frl), ptr(tanh_ws), ptr(mask), ptr(PI), ptr(aw), int(S), int(L), int(R),
+         ptr(ddot), ptr(dhoe), ptr(dfre), ptr(dctx), ptr(dfrl), ptr(dhol), stream())
+
+
+def adaatt_att_bwd_batched(ddot, PI, datten, tanh_ws, mask, aw, S, L, R, dpatt, datt, daw):
+    """the sums over the tokens: dpatt[L][R] +=, datt[L][R] +=, daw[R] +="""
+    call('l2s_adaatt_att_bwd_batched', ptr(ddot), ptr(PI), ptr(datten), ptr(tanh_ws), ptr(mask), ptr(aw), int(S), int(L), int(R),
+         ptr(dpatt), ptr(datt), ptr(daw), stream())
+
+
 def rnn_concat_fwd(hs, mask, out, T, Hh):
     """out[T][len(hs) Hh] = the directions' [T][Hh] states side by side (* mask)"""
     call('l2s_rnn_concat_fwd', ptr(hs[0]), ptr(hs[1]) if len(hs) > 1 else None, ptr(mask), ptr(out), T, Hh, len(hs), stream())

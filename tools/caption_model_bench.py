@@ -1,15 +1,16 @@
 #!/usr/bin/env python
-"""The caption branch of the full-size cycle network under --caption_model att2in2 (per-token launches, resident launch) and topdown.
+"""The caption branch of the full-size cycle network under --caption_model att2in2 (per-token launches, resident launch), topdown,
+adaatt and adaattmo.
 
 Three measurements on one device, every one with device events and the paths alternating inside each round:
   1. the captioner alone, forward and backward (+ its deferred parameter gradients), on the main stream, S = 12 tokens, on the pooled
      features of a real step;
-  2. the whole replayed train step, att2in2 against topdown (eight pipelined steps per sample);
+  2. the whole replayed train step of every captioner (eight pipelined steps per sample);
   3. from the device-clock stamps of the replayed step: when the main queue reaches the caption join and when the caption stream is done.
 
-    python tools/caption_model_bench.py [--rounds 20] [--out profiles/<name>.txt]
+    python tools/caption_model_bench.py [--rounds 20] [--out profiles/<name>.txt] [--json profiles/<name>.json]
 """
-import sys, os, argparse, collections
+import sys, os, argparse, collections, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
@@ -20,6 +21,8 @@ def main():
     ap.add_argument('--rounds', type=int, default=20)
     ap.add_argument('--tokens', type=int, default=11, help='words per caption: S = tokens + 1 captioner steps')
     ap.add_argument('--out', default='')
+    ap.add_argument('--json', default='', help='the same numbers as one JSON object')
+    ap.add_argument('--models', default='att2in2,topdown,adaatt,adaattmo')
     args = ap.parse_args()
     from lang2seg_amd.model.config import cfg
     from lang2seg_amd.nets.resnet_v1 import resnetv1
@@ -28,7 +31,7 @@ def main():
     from lang2seg_amd.loaders.synthetic_loader import SyntheticLoader
     T, V = args.tokens, 3349
     cfg.COMPUTE_DTYPE = 'bf16'
-    lines = []
+    lines, res = [], {'tokens': None, 'rounds': args.rounds, 'captioner_alone_ms': {}, 'step_ms': {}, 'join_us': {}}
 
     def say(s):
         print(s, flush=True); lines.append(s)
@@ -37,16 +40,19 @@ def main():
         opt = dict(vocab_size=V, word_embedding_size=512, word_vec_size=512, rnn_hidden_size=512, bidirectional=1, word_drop_out=0.5,
                    rnn_drop_out=0.2, rnn_num_layers=1, rnn_type='lstm', variable_lengths=1, C4_feat_dim=1024, cap_loss_weight=1.0,
                    caption_model=model, input_encoding_size=512, rnn_size=512, num_layers=1, drop_prob_lm=0.5, seq_length=T,
-                   fc_feat_size=4096, att_feat_size=4096, att_hid_size=512)
+                   fc_feat_size=4096, att_feat_size=4096, att_hid_size=512, adaatt=1)
         np.random.seed(cfg.RNG_SEED)
         net = resnetv1(opt, batch_size=1, num_layers=101)
         net.create_architecture(81, tag='default', anchor_scales=cfg.ANCHOR_SCALES, anchor_ratios=cfg.ANCHOR_RATIOS)
         net.train()
         return net, SGD(net, cfg.TRAIN.LEARNING_RATE, cfg.TRAIN.MOMENTUM, cfg.TRAIN.WEIGHT_DECAY)
     blob = SyntheticLoader(num_images=1, sents_per_image=1, H=600, W=1000, T=T, vocab_size=V).getBatch('train')
-    nets = collections.OrderedDict((m, make(m)) for m in ('att2in2', 'topdown'))
+    models = [m for m in args.models.split(',') if m]
+    nets = collections.OrderedDict((m, make(m)) for m in models)
     # ---- 1. the captioner alone ----
-    paths = [('att2in2 per-token', 'att2in2', False), ('att2in2 resident', 'att2in2', True), ('topdown', 'topdown', None)]
+    paths = [('att2in2 per-token', 'att2in2', False), ('att2in2 resident', 'att2in2', True), ('topdown', 'topdown', None),
+             ('adaatt', 'adaatt', None), ('adaattmo', 'adaattmo', None)]
+    paths = [p for p in paths if p[1] in nets]
     state = {}
     for m, (net, optim) in nets.items():
         for _ in range(2):
@@ -54,7 +60,7 @@ def main():
         torch.cuda.synchronize()
         dev = net.upload_blob(blob, 0)
         state[m] = (dev, net.t['att_feats'].clone(), net.t['fc_feats'].clone() if 'fc_feats' in net.t else None, torch.zeros(8, device='cuda'))
-    S = state['att2in2'][0]['S']
+    S = res['tokens'] = int(state[models[0]][0]['S'])
     ev = lambda: torch.cuda.Event(enable_timing=True)
 
     def run(name, m, resident):
@@ -82,16 +88,19 @@ def main():
     for _ in range(args.rounds):
         for p in paths:
             tm[p[0]].append(run(*p))
-    per_token = {'att2in2 per-token': '3 + 3', 'att2in2 resident': 'one launch per direction for all tokens', 'topdown': '5 + 5'}
+    per_token = {'att2in2 per-token': '3 + 3', 'att2in2 resident': 'one launch per direction for all tokens', 'topdown': '5 + 5',
+                 'adaatt': '1 + 1 (the attention runs once for all tokens)', 'adaattmo': '1 + 1 (the attention runs once for all tokens)'}
     for p in paths:
         a = np.array(tm[p[0]])
         say('  %-18s forward %.3f [%.3f .. %.3f]  backward + parameter gradients %.3f [%.3f .. %.3f]   launches per token (forward + backward): %s' % (
             p[0], np.median(a[:, 0]), a[:, 0].min(), a[:, 0].max(), np.median(a[:, 1]), a[:, 1].min(), a[:, 1].max(), per_token[p[0]]))
+        res['captioner_alone_ms'][p[0]] = dict(forward=float(np.median(a[:, 0])), backward=float(np.median(a[:, 1])), launches_per_token=per_token[p[0]])
     for net, _ in nets.values():
         O.memset_zero(net.P.grad)                               # the direct calls left gradients behind; the steps below start from zero
         net._cap_pre = None
     torch.cuda.synchronize()
-    nets['att2in2'][0].cap_persistent = True
+    if 'att2in2' in nets:
+        nets['att2in2'][0].cap_persistent = True
     # ---- 2. the whole replayed step ----
     for m, (net, optim) in nets.items():
         net.use_tape = True
@@ -113,6 +122,7 @@ def main():
     for m in nets:
         a = np.array(st[m])
         say('  %-10s %.3f [%.3f .. %.3f]' % (m, np.median(a), a.min(), a.max()))
+        res['step_ms'][m] = float(np.median(a))
     # ---- 3. the caption join ----
     say('caption join of the replayed step (device clock, us since the step\'s first launch, medians)')
     for m, (net, _) in nets.items():
@@ -124,9 +134,14 @@ def main():
         say('  %-10s captioner fwd done %.1f  captioner bwd done %.1f  caption stream done %.1f  main reaches the join %.1f  -> main waits %.1f' % (
             m, at('cap: captioner fwd'), at('cap: captioner bwd'), cap_done, at('main reaches the caption join'),
             max(0.0, cap_done - at('main reaches the caption join'))))
+        res['join_us'][m] = dict(captioner_fwd_done=float(at('cap: captioner fwd')), captioner_bwd_done=float(at('cap: captioner bwd')),
+                                 caption_stream_done=float(cap_done), main_reaches_join=float(at('main reaches the caption join')))
     if args.out:
         with open(args.out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(res, f, indent=1, sort_keys=True)
 
 
 if __name__ == '__main__':
