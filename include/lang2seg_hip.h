@@ -618,6 +618,38 @@ int l2s_detect_select(const void* ws, int post, int ncls, int max_per_image, flo
 int l2s_detect_paste(const float* mask_prob, int ms, l2s_det_record* rec, const int* count, int cap, int ih, int iw, uint8_t* canvases,
                      hipStream_t s);
 
+/* ---------------------------------------------------------------- caption decoding (nets/decode.py, csrc/decode.hip) ----- */
+/* Device, one workgroup.  One decision of AttModel.sample (AttModel.py:172-201) on logits[V1]: log-softmax in f32, then
+ *   sample_max != 0: the argmax (lowest index on equal values);
+ *   sample_max == 0: k drawn from p_k ~ exp(logprob_k / temperature) by inverse CDF in index order: the first k whose cumulative sum
+ *                    exceeds u * total.  u = u_in[t] when u_in is given, else 24 bits of the counter hash of (*seed_dev, salt, t).
+ * The reported log-probability is the untempered logprob[k].  *finished (device int, reset at t == 0): once a 0 was drawn every later
+ * token is 0 with log-probability 0.  Writes seq[t], seq_logprobs[t] and *next_token (what the next step's l2s_embed_fwd reads). */
+int l2s_decode_pick(const float* logits, int V1, int t, int sample_max, float temperature, const float* u_in, const uint64_t* seed_dev,
+                    uint64_t salt, int* finished, int64_t* seq, float* seq_logprobs, int64_t* next_token, hipStream_t s);
+#define L2S_BEAM_MAX 16           /* beam_size */
+#define L2S_BEAM_MAX_T 64         /* seq_length: the previous tables of a step are copied to the LDS */
+/* One completed beam, in a caller-owned device array of L2S_BEAM_RECORD_WORDS(T) 32-bit words each: seq[T] (int), logps[T] (float),
+ * p (float: the joint log-probability), index (int: the order of completion). */
+#define L2S_BEAM_RECORD_WORDS(T) (2 * (T) + 2)
+typedef struct {
+  const float* logits; int ld_logits;                    /* [B][V1] */
+  int V1, B, t, T, R, n_state;
+  int* beam_seq; float* beam_seq_logprobs; float* beam_logprobs_sum;     /* [T][B], [T][B], [B] */
+  const float* state_in[4]; float* state_out[4]; int ld_in[4], ld_out[4]; /* n_state arrays of B rows of R; in and out never overlap */
+  int64_t* next_tokens; int* parents;                    /* [B], [B] */
+  int* done; int* done_count;                            /* B * T records; device counter (reset at t == 0) */
+} l2s_beam_step_args;
+/* Device, one workgroup.  beam_step plus the completion loop of CaptionModel.py:27-121 for one t: per row the log-softmax with -1000 on
+ * the last column (:93; one row at t == 0) and its min(B, V1) best words, descending (equal values: lower index first); the candidates
+ * in column-major order with p = sum[q] + r (one f32 add), ordered by p descending, stable; the first B win.  Their histories are forked
+ * from a copy of the previous tables, the state rows gathered by parent, the B tokens written to next_tokens.  A beam whose token is 0,
+ * or any beam at t == T - 1, is appended to `done` and its sum becomes -1000.  1 <= B <= min(16, V1), T <= 64, 0 <= t < T.
+ * A NaN logit is no candidate and a NaN sum ranks last (as -inf): the outputs stay well defined and in range. */
+int l2s_decode_beam_step(const l2s_beam_step_args* a, hipStream_t s);
+/* Device.  dst [H][W] = src [ih][iw] (uint8) resized by PIL NEAREST (csrc/pil_resize.h pil_nearest_src, the rule of the loader's masks). */
+int l2s_mask_resize_nearest(const uint8_t* src, int ih, int iw, uint8_t* dst, int H, int W, hipStream_t s);
+
 /* ---------------------------------------------------------------- launch tape / streams ----- */
 /* `to` waits (device side) for everything enqueued so far on `from`; fork or join of the step's branches */
 int l2s_stream_fork(hipStream_t from, hipStream_t to);

@@ -104,6 +104,13 @@ class CapRecurBwdArgs(C.Structure):
                [(n, i32) for n in ('S', 'R', 'AH', 'L', 'ld_ddot', 'ld_datt_h')]
 
 
+class BeamStepArgs(C.Structure):
+    _fields_ = [('logits', vp), ('ld_logits', i32)] + [(n, i32) for n in ('V1', 'B', 't', 'T', 'R', 'n_state')] + \
+               [(n, vp) for n in ('beam_seq', 'beam_seq_logprobs', 'beam_logprobs_sum')] + \
+               [('state_in', vp * 4), ('state_out', vp * 4), ('ld_in', i32 * 4), ('ld_out', i32 * 4)] + \
+               [(n, vp) for n in ('next_tokens', 'parents', 'done', 'done_count')]
+
+
 class SgdSeg(C.Structure):
     _fields_ = [('offset', i64), ('count', i64), ('row_len', i32), ('weight_decay', i32), ('rowscale_off', i64),
                 ('lr_mult', f32), ('chunk0', i32), ('flags', i32), ('reserved', i32)]
@@ -203,6 +210,9 @@ SIGS = {
     'l2s_detect_nms': (i32, [vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, f32, f32, vp, vp, vp]),
     'l2s_detect_select': (i32, [vp, i32, i32, i32, f32, vp, vp, vp, i32, vp, vp]),
     'l2s_detect_paste': (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp]),
+    'l2s_decode_pick': (i32, [vp, i32, i32, i32, f32, vp, vp, u64, vp, vp, vp, vp, vp]),
+    'l2s_decode_beam_step': (i32, [C.POINTER(BeamStepArgs), vp]),
+    'l2s_mask_resize_nearest': (i32, [vp, i32, i32, vp, i32, i32, vp]),
     'l2s_lstm_step_fwd': (i32, [vp, i32, i32, vp]),
     'l2s_lstm_step_bwd': (i32, [vp, i32, i32, vp]),
     'l2s_gru_step_fwd': (i32, [vp, i32, i32, vp]),

@@ -131,11 +131,13 @@ class _Export(object):
         return out
 
 
-def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1, detect=None):
+def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1, detect=None, caption=None):
     """every sentence of one image through the device path; record base + i for sentence i.  No host synchronisation.
     pool_words >= 0 or None: also keep the predictions on the device (None: the default pool budget) -> the image's _Export.
     detect: None, or a dict (max_per_image, thresh) that asks for every detection of each sentence too (model/detect_device.py) and
-    receives 'detector' (the image's _Detector) and 'sentence' (forward_test_sentence of sentence i again, for its re-runs)"""
+    receives 'detector' (the image's _Detector) and 'sentence' (forward_test_sentence of sentence i again, for its re-runs)
+    caption: None, or a callable (i, the sentence's outputs, the image's _Export) run behind sentence i's mask, while the sentence's
+    buffers are still its own (model/caption_device.py)"""
     img, lab_d, lens, box_d, gm = _upload_image(net, data, n_sent)
     im_info = np.asarray(data['im_info'], dtype=np.float32).reshape(-1)[:3]
     scale, ih, iw = _geometry(im_info)
@@ -167,6 +169,8 @@ def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1, detect=
             O.eval_mask_iou(mprob, rec, base + i, gm[i], ih, iw, canvas=None if ex is None else ex.canvas[i])
             if ex is not None:
                 ex.encode(i)
+        if caption is not None:
+            caption(i, s, ex)
         if det is not None:                                   # last: its mask head pass reuses the heads' buffers
             det.run(i, s)
     return ex

@@ -36,7 +36,13 @@ def core_fwd(O, pv, B, xpre, fcrow, att, patt, masks, S, L, R, G):
     w_hh, b_hh, w_r, b_r = pv('lstm.h2h.0.weight'), pv('lstm.h2h.0.bias'), pv('lstm.r_h2h.weight'), pv('lstm.r_h2h.bias')
     for i in range(S):
         O.adaatt_cell_fwd(xpre[i], fcrow, w_hh, b_hh, w_r, b_r, hs[i], cs[i], cs[i + 1], hs[i + 1], B['fake'][i], B['save'][i], R, G)
-    toph = _masked(O, hs[1:], masks.get('toph'), B['toph'])
+    return att_fwd(O, pv, B, hs[1:], att, patt, masks, S, L, R)
+
+
+def att_fwd(O, pv, B, h, att, patt, masks, S, L, R):
+    """the attention half of core_fwd on S rows of cell outputs h [S][R] and B['fake'] (S tokens of one sentence, or the S beams of one
+    decoding step: the rows never meet)"""
+    toph = _masked(O, h, masks.get('toph'), B['toph'])
     faked = _masked(O, B['fake'], masks.get('fake'), B['faked'])
     lin = lambda x, k, y, act=0: O.linear_fwd(x, pv('attention.%s.weight' % k), pv('attention.%s.bias' % k), y, S, R, R, act=act)
     lin(faked, 'fr_linear.0', B['fra'], 1)

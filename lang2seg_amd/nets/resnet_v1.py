@@ -1473,6 +1473,8 @@ class resnetv1(Network):
             rois[:fr.shape[0]].copy_(fr); n_forced = int(fr.shape[0])
         # heads run on all `post` slots (static shapes); rows >= nkeep are padding
         cheads, cls_prob, bbox_pred, mprob = self._roi_heads_test(net_conv, Hc, Wc, rois, post)
+        # what caption_features reads of this sentence (no launch: the buffers stay as they are until the next sentence)
+        self._test_sentence = dict(net_conv=net_conv, net_conv_hw=(Hc, Wc), base=base, blob_hw=(int(d['data'].shape[1]), int(d['data'].shape[2])))
         return dict(net_conv=net_conv, net_conv_hw=(Hc, Wc), response=resp, rois=rois, own_rois=own, nkeep=nkeep, n_forced=n_forced, post=post,
                     cheads=cheads, cls_prob=cls_prob, bbox_pred=bbox_pred, mask_prob=mprob, rpn_cls_prob=prob)
 
@@ -1523,3 +1525,54 @@ class resnetv1(Network):
             mk = lambda v: torch.tensor(list(v), dtype=f32, device=self.device)
             self._cst = dict(means=mk(TR.BBOX_NORMALIZE_MEANS), stds=mk(TR.BBOX_NORMALIZE_STDS), inw=mk(TR.BBOX_INSIDE_WEIGHTS))
         return self._cst
+
+    # ------------------------------------------------------------------ mask -> sentence (AttModel.py:103-209, CaptionModel.py:23-124)
+    def caption_features(self, mask_u8=None):
+        """(att_feats [196][att_feat_size], fc_feats [fc_feat_size] or None) of the sentence whose TEST forward ran last (forward_test_sentence),
+        by the launches of the training branch: layer4 on the map, the mask at the map's size, the 14x14 and the one-bin pooling.
+        mask_u8: a blob-sized uint8 mask (network 'cycle'; unused on 'cycle_response', which pools the map before and after the gating)."""
+        if self.var['cap'] is None or not hasattr(self, 'att_embed') or not getattr(self, 'layers', {}).get(4):
+            raise ValueError('--variant %s has no caption branch to take features for (cycle and cycle_response on a ResNet have one)' % self.variant)
+        p = getattr(self, '_test_sentence', None)
+        if p is None:
+            raise RuntimeError('caption_features follows forward_test_sentence: no TEST forward has run')
+        net_conv, (Hc, Wc), (H, W) = p['net_conv'], p['net_conv_hw'], p['blob_hw']
+        AF = self.opt['att_feat_size']
+
+        def l4_on_map(x, tag):
+            hh, ww = Hc, Wc
+            for b, blk in enumerate(self.layers[4]):
+                x, hh, ww, _ = blk.fwd(x, 1, hh, ww, '%s.%d' % (tag, b))
+            return x
+        feats = l4_on_map(net_conv, 'l4m')
+        att = self.buf('cap.att', (196, AF))
+        fc = None
+        if self.cap_model in FC_CAPTIONERS:
+            FC = self.opt['fc_feat_size']
+            if FC != 2 * 2048:
+                raise ValueError('fc_feat_size %r: fc_feats is the pair of 2048-channel means of layer4 on the map (4096)' % (FC,))
+            fc = self.buf('cap.fc', (FC,))
+        if self.var['cap'] == 'mask':
+            if mask_u8 is None or mask_u8.dtype != torch.uint8 or mask_u8.numel() != H * W:
+                raise ValueError('caption_features: the cycle network pools under a uint8 mask of the blob\'s size %d x %d' % (H, W))
+            gm = self.buf('cap.gm', (Hc * Wc,), f32)
+            O.mask_downsample(mask_u8, gm, H, W, Hc, Wc)
+            O.adaptive_pool_fwd(feats, None, att, Hc, Wc, 2048, 14, 14, AF)
+            O.adaptive_pool_fwd(feats, gm, att[:, 2048:], Hc, Wc, 2048, 14, 14, AF)
+            if fc is not None:
+                O.adaptive_pool_fwd(feats, None, fc, Hc, Wc, 2048, 1, 1, FC)
+                O.adaptive_pool_fwd(feats, gm, fc[2048:], Hc, Wc, 2048, 1, 1, FC)
+        else:
+            feats_b = l4_on_map(p['base'], 'l4b')
+            O.adaptive_pool_fwd(feats_b, None, att, Hc, Wc, 2048, 14, 14, AF)
+            O.adaptive_pool_fwd(feats, None, att[:, 2048:], Hc, Wc, 2048, 14, 14, AF)
+            if fc is not None:
+                O.adaptive_pool_fwd(feats_b, None, fc, Hc, Wc, 2048, 1, 1, FC)
+                O.adaptive_pool_fwd(feats, None, fc[2048:], Hc, Wc, 2048, 1, 1, FC)
+        return att, fc
+
+    def caption_decode(self, att_feats, fc_feats=None, sample_max=1, beam_size=1, temperature=1.0):
+        """greedy (sample_max = 1), sampled (sample_max = 0, temperature) or beam-search (beam_size > 1) decoding of the selected captioner on
+        the device, eval mode: {'seq', 'logprobs'} (+ 'beams' for beam search).  nets/decode.py"""
+        from . import decode
+        return decode.caption_decode(self, att_feats, fc_feats, sample_max, beam_size, temperature)

@@ -757,6 +757,53 @@ def detect_paste(mask_prob, rec, count, ih, iw, canvases):
     call('l2s_detect_paste', ptr(mask_prob), ms, ptr(rec), ptr(count), cap, ih, iw, ptr(canvases), stream())
 
 
+# ------------------------------------------------------------------ caption decoding (csrc/decode.hip)
+BEAM_MAX, BEAM_MAX_T = 16, 64
+
+
+def decode_pick(logits, V1, t, sample_max, temperature, u, seed_dev, salt, finished, seq, seq_logprobs, next_token):
+    """one decision of AttModel.sample on logits f32 [V1]: argmax (sample_max) or an inverse-CDF draw with u[t] (u f32 [T], injected) or the
+    counter hash of (seed_dev, salt, t); finished int32 [1], seq int64 [T], seq_logprobs f32 [T], next_token int64 [1]"""
+    if logits.numel() < V1 or seq.numel() <= t or seq_logprobs.numel() <= t or (u is not None and u.numel() <= t):
+        raise ValueError('decode_pick: a buffer is smaller than V1 = %d / t = %d asks' % (V1, t))
+    call('l2s_decode_pick', ptr(logits), int(V1), int(t), 1 if sample_max else 0, float(temperature), ptr(u), ptr(seed_dev), int(salt),
+         ptr(finished), ptr(seq), ptr(seq_logprobs), ptr(next_token), stream())
+
+
+def beam_record_words(T):
+    return 2 * T + 2
+
+
+def decode_beam_step(logits, V1, B, t, T, beam_seq, beam_seq_logprobs, beam_logprobs_sum, states, R, next_tokens, parents, done, done_count,
+                     ld_logits=None):
+    """beam_step + the completion loop of CaptionModel.beam_search for one t.  logits f32 [B][V1]; beam_seq int32 [T][B], beam_seq_logprobs
+    f32 [T][B], beam_logprobs_sum f32 [B]; states: up to four (in, out, ld_in, ld_out) of B rows of R floats, gathered by parent; next_tokens
+    int64 [B], parents int32 [B]; done int32 [B * T][2 T + 2] (seq | logps | p | completion index), done_count int32 [1]"""
+    if not 1 <= B <= BEAM_MAX:
+        raise ValueError('--beam_size %r: 1 .. %d' % (B, BEAM_MAX))
+    ld = V1 if ld_logits is None else ld_logits
+    if (logits.numel() < (B - 1) * ld + V1 or beam_seq.numel() < T * B or beam_seq_logprobs.numel() < T * B or beam_logprobs_sum.numel() < B or
+            next_tokens.numel() < B or parents.numel() < B or done.numel() < B * T * beam_record_words(T) or done_count.numel() < 1):
+        raise ValueError('decode_beam_step: a buffer is smaller than B = %d, T = %d, V1 = %d ask' % (B, T, V1))
+    a = _lib.BeamStepArgs()
+    a.logits, a.ld_logits, a.V1, a.B, a.t, a.T, a.R, a.n_state = ptr(logits), int(ld), int(V1), int(B), int(t), int(T), int(R), len(states)
+    a.beam_seq, a.beam_seq_logprobs, a.beam_logprobs_sum = ptr(beam_seq), ptr(beam_seq_logprobs), ptr(beam_logprobs_sum)
+    assert len(states) <= 4
+    for j, (si, so, li, lo) in enumerate(states):
+        if si.numel() < B * R or so.numel() < B * R or li < R or lo < R:
+            raise ValueError('decode_beam_step: state %d is smaller than B = %d rows of R = %d' % (j, B, R))
+        a.state_in[j], a.state_out[j], a.ld_in[j], a.ld_out[j] = ptr(si), ptr(so), int(li), int(lo)
+    a.next_tokens, a.parents, a.done, a.done_count = ptr(next_tokens), ptr(parents), ptr(done), ptr(done_count)
+    call('l2s_decode_beam_step', C.byref(a), stream())
+
+
+def mask_resize_nearest(src, ih, iw, dst, H, W):
+    """dst uint8 [H][W] = src uint8 [ih][iw] resized by PIL NEAREST, the rule of the loader's ground-truth masks"""
+    if src.numel() < ih * iw or dst.numel() < H * W:
+        raise ValueError('mask_resize_nearest: a mask is smaller than its shape')
+    call('l2s_mask_resize_nearest', ptr(src), int(ih), int(iw), ptr(dst), int(H), int(W), stream())
+
+
 def rcnn_predict(heads, ldh, R, ncls, stds4, means4, cls_prob, bbox_pred):
     call('l2s_rcnn_predict', ptr(heads), ldh, R, ncls, ptr(stds4), ptr(means4), ptr(cls_prob), ptr(bbox_pred), stream())
 

@@ -9,6 +9,12 @@ Three measurements on one device, every one with device events and the paths alt
   3. from the device-clock stamps of the replayed step: when the main queue reaches the caption join and when the caption stream is done.
 
     python tools/caption_model_bench.py [--rounds 20] [--out profiles/<name>.txt] [--json profiles/<name>.json]
+
+--decode measures caption decoding instead (Network.caption_decode, nets/decode.py): time per caption by device events at rnn_size 512,
+vocab_size 1999, seq_length 10 for every captioner, greedy and beam 3, interleaved rounds after a warm-up, medians; and the launches per
+caption, counted by recording one call on a launch tape.
+
+    python tools/caption_model_bench.py --decode [--rounds 20] [--json profiles/r09_decode_bench.json]
 """
 import sys, os, argparse, collections, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,7 +29,10 @@ def main():
     ap.add_argument('--out', default='')
     ap.add_argument('--json', default='', help='the same numbers as one JSON object')
     ap.add_argument('--models', default='att2in2,topdown,adaatt,adaattmo')
+    ap.add_argument('--decode', action='store_true', help='time caption decoding (greedy and beam 3) instead of the training branch')
     args = ap.parse_args()
+    if args.decode:
+        return decode_bench(args)
     from lang2seg_amd.model.config import cfg
     from lang2seg_amd.nets.resnet_v1 import resnetv1
     from lang2seg_amd.optim import SGD
@@ -136,6 +145,70 @@ def main():
             max(0.0, cap_done - at('main reaches the caption join'))))
         res['join_us'][m] = dict(captioner_fwd_done=float(at('cap: captioner fwd')), captioner_bwd_done=float(at('cap: captioner bwd')),
                                  caption_stream_done=float(cap_done), main_reaches_join=float(at('main reaches the caption join')))
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+
+
+def decode_bench(args):
+    from lang2seg_amd.model.config import cfg
+    from lang2seg_amd.nets.resnet_v1 import resnetv1
+    from lang2seg_amd import ops as O
+    T, V, R = 10, 1999, 512
+    cfg.COMPUTE_DTYPE = 'bf16'
+    models = [m for m in args.models.split(',') if m]
+    modes = [('greedy', dict(beam_size=1)), ('beam 3', dict(beam_size=3))]
+    nets = {}
+    for m in models:
+        opt = dict(vocab_size=V, word_embedding_size=512, word_vec_size=512, rnn_hidden_size=512, bidirectional=1, word_drop_out=0.5,
+                   rnn_drop_out=0.2, rnn_num_layers=1, rnn_type='lstm', variable_lengths=1, C4_feat_dim=1024, cap_loss_weight=1.0,
+                   caption_model=m, input_encoding_size=R, rnn_size=R, num_layers=1, drop_prob_lm=0.5, seq_length=T,
+                   fc_feat_size=4096, att_feat_size=4096, att_hid_size=R, adaatt=1)
+        np.random.seed(cfg.RNG_SEED)
+        net = resnetv1(opt, batch_size=1, num_layers=101)
+        net.create_architecture(81, tag='default', anchor_scales=cfg.ANCHOR_SCALES, anchor_ratios=cfg.ANCHOR_RATIOS)
+        net.eval()
+        nets[m] = net
+    g = torch.Generator().manual_seed(1)
+    att = torch.randn(196, 4096, generator=g).abs().to(torch.bfloat16).cuda()         # pooled ReLU outputs: non-negative
+    fc = torch.randn(4096, generator=g).abs().to(torch.bfloat16).cuda()
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+    res = dict(rnn_size=R, vocab_size=V, seq_length=T, rounds=args.rounds, dtype='bf16 network, fp32 captioner', ms_per_caption={}, launches_per_caption={},
+               words={})
+    lines = []
+
+    def say(s):
+        print(s, flush=True); lines.append(s)
+    for m, net in nets.items():
+        for name, kw in modes:
+            for _ in range(3):                                     # warm-up: buffers, code objects
+                r = net.caption_decode(att, fc, **kw)
+            torch.cuda.synchronize()
+            h = O.tape_begin([torch.cuda.current_stream()] + list(net.streams().values()))     # (the joins in front of the head touch the side streams)
+            try:
+                net.caption_decode(att, fc, **kw)
+            finally:
+                O.tape_end(h)
+            res['launches_per_caption']['%s %s' % (m, name)] = O.tape_size(h)
+            res['words']['%s %s' % (m, name)] = len(r['seq'])
+            O.tape_destroy(h)
+    tm = {'%s %s' % (m, name): [] for m in nets for name, _ in modes}
+    for _ in range(args.rounds):
+        for m, net in nets.items():
+            for name, kw in modes:
+                a, b = ev(), ev()
+                a.record(); net.caption_decode(att, fc, **kw); b.record()
+                torch.cuda.synchronize()
+                tm['%s %s' % (m, name)].append(a.elapsed_time(b))
+    say('caption decoding, rnn_size %d, vocab_size %d, seq_length %d, %d interleaved rounds; ms per caption (device events around the call, its one '
+        'read-back included), median [min .. max]; launches per caption (tape ops: kernels, clears, the counter)' % (R, V, T, args.rounds))
+    for k, v in tm.items():
+        a = np.array(v)
+        say('  %-18s %.3f [%.3f .. %.3f]   %d launches' % (k, np.median(a), a.min(), a.max(), res['launches_per_caption'][k]))
+        res['ms_per_caption'][k] = float(np.median(a))
     if args.out:
         with open(args.out, 'w') as f:
             f.write('\n'.join(lines) + '\n')

@@ -6,7 +6,13 @@ Prints one JSON list: per sentence the class, the box, the score, the mask's are
 each mask as DIR/<image>_<sent_index>.png, decoded on the device from the run lengths (l2s_rle_to_mask): the round trip.
     --all_detections 1 [--max_per_image N] [--det_thresh T]: every instance the network finds for each sentence instead of its first
 pick (model/detect_device.py: class-wise NMS with cfg.TEST.NMS, the best N over all classes); prints one list per sentence, --png writes
-DIR/<image>_<sent_index>_<k>.png."""
+DIR/<image>_<sent_index>_<k>.png.
+    --caption 1 [--beam_size B] [--sample_max 0|1] [--temperature t]: also what the captioner says about each predicted mask
+(model/caption_device.py: the caption branch's features under the mask, decoded on the device: greedy by default, sampled with
+--sample_max 0, beam search with --beam_size > 1); adds caption_tokens, caption_logprobs and caption to every sentence's dict.  The
+captioner is the snapshot's: --caption_model (with --adaatt 1 for adaatt / adaattmo) and the size flags as the train tools take them.  With
+--synthetic 1 the words print as w<id>.  --beam_size > 1 is beam search whatever --sample_max says, as in the reference; --caption 1 together
+with --all_detections 1 is an error."""
 import argparse
 import json
 import os
@@ -35,6 +41,12 @@ def parse_args(argv=None):
     # (default None: tools/opt.py's own defaults apply)
     p.add_argument('--rnn_type', default=None, help='lstm, gru or rnn'); p.add_argument('--rnn_num_layers', type=int, default=None)
     p.add_argument('--bidirectional', type=int, default=None)
+    # mask -> sentence; the captioner flags of tools/opt.py (default None: its own defaults)
+    p.add_argument('--caption', type=int, default=0); p.add_argument('--beam_size', type=int, default=1)
+    p.add_argument('--sample_max', type=int, default=1); p.add_argument('--temperature', type=float, default=1.0)
+    p.add_argument('--caption_model', default=None); p.add_argument('--adaatt', type=int, default=None)
+    for k in ('rnn_size', 'input_encoding_size', 'att_hid_size', 'fc_feat_size', 'att_feat_size'):
+        p.add_argument('--' + k, type=int, default=None)
     return vars(p.parse_args(argv))
 
 
@@ -53,6 +65,8 @@ def write_png(pred, path):
 
 
 def main(args):
+    if args.get('all_detections') and args.get('caption'):
+        raise ValueError('--caption 1 with --all_detections 1: a caption describes the one mask picked for a sentence, not each detection; give one of the two')
     from lang2seg_amd import ops as O
     from lang2seg_amd.model.config import cfg, cfg_from_file
     from lang2seg_amd.model.predict_device import predict_image
@@ -82,7 +96,8 @@ def main(args):
         data = dict(data=blob.cpu().numpy(), im_info=np.array([[oh, ow, sc]], np.float32), file_name=osp.basename(args['image']))
     opt = parse_opt([])
     opt.update(vocab_size=loader.vocab_size, C4_feat_dim=1024, seq_length=loader.label_length, dataset_splitBy=name)
-    opt.update({k: args[k] for k in ('rnn_type', 'rnn_num_layers', 'bidirectional') if args.get(k) is not None})
+    opt.update({k: args[k] for k in ('rnn_type', 'rnn_num_layers', 'bidirectional', 'caption_model', 'adaatt', 'rnn_size', 'input_encoding_size',
+                                     'att_hid_size', 'fc_feat_size', 'att_feat_size') if args.get(k) is not None})
     if args['variant'] == 'vgg':
         from lang2seg_amd.nets.vgg16 import vgg16
         opt['C4_feat_dim'] = 512
@@ -106,7 +121,16 @@ def main(args):
                         write_png(p, osp.join(args['png'], '%s_%d_%d.png' % (osp.splitext(p['file_name'])[0], p['sent_index'], k)))
         print(json.dumps(dets))
         return dets
-    preds = predict_image(net, data, labels)
+    if args.get('caption'):
+        from lang2seg_amd.model.caption_device import caption_image
+        if args['synthetic']:
+            words = {str(i): 'w%d' % i for i in range(1, loader.vocab_size + 1)}
+        else:
+            words = loader.ix_to_word
+        preds = caption_image(net, data, labels, sample_max=args['sample_max'], beam_size=args['beam_size'], temperature=args['temperature'],
+                              ix_to_word=words)
+    else:
+        preds = predict_image(net, data, labels)
     if args['png']:
         os.makedirs(args['png'], exist_ok=True)
         for p in preds:
