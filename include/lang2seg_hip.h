@@ -70,6 +70,9 @@ typedef struct {
 int l2s_conv_igemm(const l2s_conv_desc* d, int dtype, hipStream_t stream);
 /* name of the kernel l2s_conv_igemm launches for this problem (reporting: bench.py's roofline object); static storage */
 const char* l2s_conv_plan_name(const l2s_conv_desc* d, int dtype);
+/* for tests and reports only: the kernel of the calling thread's latest launch, as the launch site names it (template arguments
+ * included); static storage, NULL before the thread's first launch.  Nothing reads it to decide anything. */
+const char* l2s_last_kernel(void);
 
 /* weight gradient: dw[Cout][KH*KW*Cin] (float) += sum_pixels dy[p][co] * x(p,tap)[ci]
  * (cuDNN backward-filter behind autograd in the reference: resnet_v1_cycle_res5_2.py:83-88,324-335, network_cycle_res5_2.py:236-251,279-301).

@@ -123,6 +123,7 @@ LOSS_RPN_CLS, LOSS_RPN_BOX, LOSS_CLS, LOSS_BOX, LOSS_MASK, LOSS_CAP, LOSS_TOTAL,
 SIGS = {
     'l2s_version': (i32, []),
     'l2s_conv_plan_name': (C.c_char_p, [vp, i32]),
+    'l2s_last_kernel': (C.c_char_p, []),
     'l2s_roialign_block0_fwd': (i32, [C.POINTER(RoiBlock0Desc), vp]),
     'l2s_conv_igemm': (i32, [C.POINTER(ConvDesc), i32, vp]),
     'l2s_conv_wgrad': (i32, [C.POINTER(WgradDesc), i32, vp]),

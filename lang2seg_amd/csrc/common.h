@@ -101,10 +101,12 @@ __device__ __forceinline__ int fast_div(int a, int b, float rb) {
 namespace l2s {
 bool recording();
 void record(hipStream_t s, std::function<void(hipStream_t)> fn);
+extern thread_local const char* last_kernel;   // the kernel argument of this thread's latest L2S_LAUNCH, as written (l2s_last_kernel: reports only)
 }
 #define L2S_LAUNCH(kern, grid, block, shmem, stream, ...)                                                              \
   do {                                                                                                                \
     if (l2s::recording()) l2s::record((stream), [=](hipStream_t s_) { hipLaunchKernelGGL(kern, grid, block, shmem, s_, __VA_ARGS__); }); \
+    l2s::last_kernel = #kern;                                                                                         \
     hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);                                                 \
   } while (0)
 

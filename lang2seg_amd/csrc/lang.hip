@@ -80,11 +80,11 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict
   }
 }
 
-// dx[m][k] (+)= sum_n dy[m][n] w[n][k]  (transposed GEMV): block = 64 k-columns (one per lane) x 16 n-groups
+// dx[m][k] (+)= (sum_n dy[m][n] w[n][k]) (* mul[m][k])  (transposed GEMV): block = 64 k-columns (one per lane) x 16 n-groups
 // (one per wave); every wave streams whole 256-byte rows of w; cross-wave reduction through LDS; no atomics.
 template <int MT>
 __global__ __launch_bounds__(1024) void gemvT_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ w, float* dx,
-                                                    int lddx, int m0, int M, int N, int K, int accumulate) {
+                                                    int lddx, int m0, int M, int N, int K, int accumulate, const float* __restrict__ mul) {
   __shared__ float sh[MT][16][64];
   const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int k = blockIdx.x * 64 + lane;
@@ -109,6 +109,7 @@ __global__ __launch_bounds__(1024) void gemvT_kernel(const float* __restrict__ d
       float s = 0.f;
 #pragma unroll
       for (int j = 0; j < 16; ++j) s += sh[m][j][l];
+      if (mul) s *= mul[(long)(m0 + m) * lddx + kk];     // the product alone, as in the MFMA kernels: what dx held is added after it
       float* out = dx + (long)(m0 + m) * lddx + kk;
       *out = accumulate ? (*out + s) : s;
     }
@@ -439,10 +440,6 @@ __global__ __launch_bounds__(1024) void lsm_nll_kernel(const float* logits, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-__global__ void mul_inplace_kernel(float* dx, int lddx, const float* __restrict__ mul, int M, int K) {
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i < (long)M * K) { const int m = (int)(i / K), k = (int)(i - (long)m * K); dx[(long)m * lddx + k] *= mul[(long)m * lddx + k]; }
-}
 // Row-batch linears on the exact-fp32 MFMA (v_mfma_f32_16x16x4_f32: a lane holds A[l%16][l/16] and B[l/16][l%16], D rows 4(l/16)+r).
 // The wave-per-output kernels above re-read the x block per output and leave the 21 x 3350 x 512 logit layer at 40-200 us; these
 // stream every weight exactly once with 16-byte loads, 4 k (or n) per lane per load: the MFMA's k index is a permutation of memory
@@ -674,7 +671,8 @@ extern "C" int l2s_linear_fwd(const float* x, int ldx_, const float* w, int ldw,
                     else L2S_LAUNCH((linear_fwd_kernel<MT, 1, NW>), grid, dim3(256), 0, s, x, ldx_, w, ldw, b, y, ldy, m0, M, N, K, act, accumulate); } while (0)
     // NW = 4 (x reused for four outputs) was measured slower inside the step (635 vs 441 us for the 11 row-batch launches: four times
     // fewer waves to hide the load latency on 512..3350 outputs), so every wave keeps one output
-    if (M <= 1) LF(1, 1); else if (M <= 8) LF(8, 1); else if (M <= 16) LF(16, 1); else LF(MAXM, 1);
+    static_assert(MAXM == 24, "the last form below is written as a number so that l2s_last_kernel names the instantiation");
+    if (M <= 1) LF(1, 1); else if (M <= 8) LF(8, 1); else if (M <= 16) LF(16, 1); else LF(24, 1);
 #undef LF
   }
   return l2s_check_launch();
@@ -708,9 +706,8 @@ extern "C" int l2s_linear_bwd_x(const float* dy, int lddy, const float* w, float
     return l2s_check_launch();
   }
   dim3 grid(cdiv(K, 64));
-  if (M == 1) L2S_LAUNCH(gemvT_kernel<1>, grid, dim3(1024), 0, s, dy, lddy, w, dx, lddx, 0, M, N, K, accumulate);
-  else for (int m0 = 0; m0 < M; m0 += 8) L2S_LAUNCH(gemvT_kernel<8>, grid, dim3(1024), 0, s, dy, lddy, w, dx, lddx, m0, M, N, K, accumulate);
-  if (mul) L2S_LAUNCH(mul_inplace_kernel, dim3(cdiv((long)M * K, 256)), dim3(256), 0, s, dx, lddx, mul, M, K);
+  if (M == 1) L2S_LAUNCH(gemvT_kernel<1>, grid, dim3(1024), 0, s, dy, lddy, w, dx, lddx, 0, M, N, K, accumulate, mul);
+  else for (int m0 = 0; m0 < M; m0 += 8) L2S_LAUNCH(gemvT_kernel<8>, grid, dim3(1024), 0, s, dy, lddy, w, dx, lddx, m0, M, N, K, accumulate, mul);
   return l2s_check_launch();
 }
 extern "C" int l2s_linear_bwd_w(const float* dy, int lddy, const float* x, int ldx_, float* dw, float* db, int M, int N, int K, hipStream_t s) {

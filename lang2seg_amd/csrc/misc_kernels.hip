@@ -725,7 +725,7 @@ extern "C" int l2s_avgpool_fwd(const void* x, void* y, int n_img, int hw, int C,
 }
 extern "C" int l2s_avgpool_bwd(const void* dy, void* dx, const void* addend, const void* ref, int n_img, int hw, int C, int dtype, hipStream_t s) {
   long total = (long)n_img * hw * C;
-  if (dtype == L2S_BF16 && (C & 7) == 0) {
+  if (dtype == L2S_BF16 && (C & 7) == 0 && !((uintptr_t)dy & 15) && !((uintptr_t)dx & 15) && !((uintptr_t)addend & 15) && !((uintptr_t)ref & 15)) {
     L2S_LAUNCH(avgpool_bwd_bf16x8_kernel, dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)dy, (bf16_t*)dx, (const bf16_t*)addend, (const bf16_t*)ref, hw, C, total / 8);
     return l2s_check_launch();
   }

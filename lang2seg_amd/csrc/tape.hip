@@ -44,6 +44,7 @@ static int stream_id(hipStream_t s) {
   return -1;
 }
 bool recording() { return g_rec != nullptr && !g_paused; }
+thread_local const char* last_kernel = nullptr;
 void record(hipStream_t s, std::function<void(hipStream_t)> fn) {
   if (!g_rec || g_paused) return;
   g_rec->ops.push_back(Op{0, stream_id(s), -1, std::move(fn)});
@@ -52,6 +53,8 @@ void record(hipStream_t s, std::function<void(hipStream_t)> fn) {
 }  // namespace l2s
 
 using namespace l2s;
+
+extern "C" const char* l2s_last_kernel(void) { return l2s::last_kernel; }
 
 extern "C" void* l2s_tape_begin(const hipStream_t* streams, int n) {
   if (g_rec || n < 1 || n > 8) return nullptr;

@@ -97,6 +97,13 @@ def tape_size(h):
     return int(_lib.load().l2s_tape_size(h))
 
 
+def last_kernel():
+    """tests and reports only: the kernel of this thread's latest launch as its launch site names it, without blanks or the macro's
+    parentheses ('linear_fwd_kernel<8,2,1>'); None before the first launch"""
+    n = _lib.load().l2s_last_kernel()
+    return None if n is None else n.decode().replace(' ', '').strip('()')
+
+
 # ------------------------------------------------------------------ conv / gemm
 # kernel family of every convolution that does not name one (l2s_conv_desc.algo: 0 = auto); set by the benchmark tools only
 # (bench.py --conv-algo, tools/*bench*.py): same arithmetic, speed only
