@@ -5,9 +5,9 @@ never the next token, so it runs ONCE for all S tokens as row batches: the small
 weighted sum with the token as a grid dimension.  Backward mirrors it: the attention's backward for all tokens first (d(att) and d(p_att) are
 complete before the recurrence starts), then S cell launches from the last token to the first.
 
-Used by nets/resnet_v1.py (_adaatt_fwd / _adaatt_bwd) and, with plain tensors, by tests/test_adaatt_gpu.py.  `O` is lang2seg_amd.ops (or its
-torch restatement), pv / gv give a parameter / its gradient by the key below 'caption_model.core.', `bwd_x` is Network.bwd_x's signature with
-that key.  Masks: {'toph', 'fake', 'frl', 'hol': [S][R], 'hA': [S][L+1][R]}, each None when dropout is off."""
+Used by nets/captioners.py (AdaAtt; decoding runs cell_fwd and att_fwd on its beam rows) and, with plain tensors, by
+tests/test_adaatt_gpu.py.  `O` is lang2seg_amd.ops (or its torch restatement), pv / gv give a parameter / its gradient by the key below
+'caption_model.core.', `bwd_x` is Network.bwd_x's with that key.  Masks: {'toph', 'fake', 'frl', 'hol': [S][R], 'hA': [S][L+1][R]} or None."""
 
 
 def fwd_shapes(S, L, R):
@@ -29,13 +29,20 @@ def _masked(O, x, m, out):
     return out
 
 
+CELL_KEYS = ('lstm.h2h.0.weight', 'lstm.h2h.0.bias', 'lstm.r_h2h.weight', 'lstm.r_h2h.bias')      # what cell_fwd takes as `w`, in its order
+
+
+def cell_fwd(O, w, xpre, fcrow, h0, c0, h1, c1, fake, save, R, G):
+    """the cell on one row: token i of a sentence (core_fwd) or one beam of a decoding step.  (h0, c0) -> (h1, c1), the sentinel into fake"""
+    O.adaatt_cell_fwd(xpre, fcrow, w[0], w[1], w[2], w[3], h0, c0, c1, h1, fake, save, R, G)
+
+
 def core_fwd(O, pv, B, xpre, fcrow, att, patt, masks, S, L, R, G):
     """xpre [S][(G+1)R] = w2h(xt) | r_w2h(xt) (biases included), fcrow [(G+1)R] = v2h(fc) | r_v2h(fc); att / patt [L][R]; B: fwd_shapes buffers,
     hs / cs row 0 zero.  Leaves the outputs tanh(att2h(atten)) [S][R] in B['outs'] and returns the views backward needs."""
-    hs, cs = B['hs'], B['cs']
-    w_hh, b_hh, w_r, b_r = pv('lstm.h2h.0.weight'), pv('lstm.h2h.0.bias'), pv('lstm.r_h2h.weight'), pv('lstm.r_h2h.bias')
+    hs, cs, w = B['hs'], B['cs'], tuple(pv(k) for k in CELL_KEYS)
     for i in range(S):
-        O.adaatt_cell_fwd(xpre[i], fcrow, w_hh, b_hh, w_r, b_r, hs[i], cs[i], cs[i + 1], hs[i + 1], B['fake'][i], B['save'][i], R, G)
+        cell_fwd(O, w, xpre[i], fcrow, hs[i], cs[i], hs[i + 1], cs[i + 1], B['fake'][i], B['save'][i], R, G)
     return att_fwd(O, pv, B, hs[1:], att, patt, masks, S, L, R)
 
 

@@ -13,9 +13,11 @@ from .. import ops as O
 from .._lib import F32, BF16
 from ..model.config import cfg
 from .network import Network, ConvOp, Bottleneck
-from .params import ParamStore, encoder_config, caption_config, ADAATT_GATES, FC_CAPTIONERS
+from .params import ParamStore, encoder_config, caption_config
+from .captioners import CAPTIONERS
 from .variants import solver_cfg
 from . import anchors as ANC
+from . import decode
 
 f32 = torch.float32
 
@@ -34,6 +36,7 @@ class resnetv1(Network):
         self.enc = encoder_config(self.opt)      # (rnn_type, layers, directions, gate rows per unit); ValueError names a rejected option
         # the captioner --caption_model names (nets/params.py CAPTIONERS; ValueError otherwise); networks without a caption branch ignore the option
         self.cap_model = caption_config(self.opt) if self.var['cap'] is not None else None
+        self.captioner = CAPTIONERS[self.cap_model](self) if self.cap_model is not None else None     # nets/captioners.py
         self._cap_loss_weight = float(self.opt.get('cap_loss_weight', 0.0)) if self.var['cap'] is not None else 0.0   # RES:253
         self._C4_feat_dim = self.opt['C4_feat_dim']
 
@@ -131,18 +134,8 @@ class resnetv1(Network):
         # only the matrices whose data gradient is taken one row at a time (inside a recurrence); row batches use bwd_x's MFMA path
         for w in self._encoder_hh_keys():
             add(w, P.view(w), *P.shapes[w])
-        if self.cap_model == 'topdown':
-            # both cells' matrices (att_lstm.weight_ih: its h_lang and fc column blocks, rows of the transposed copy) and h2att
-            capk = ['caption_model.core.%s' % k for k in ('att_lstm.weight_ih', 'att_lstm.weight_hh', 'lang_lstm.weight_ih', 'lang_lstm.weight_hh',
-                                                          'attention.h2att.weight')]
-        elif self.cap_model in ADAATT_GATES:
-            capk = ['caption_model.core.lstm.h2h.0.weight', 'caption_model.core.lstm.r_h2h.weight']     # what token i + 1 reads of h(i)
-        else:
-            capk = ['caption_model.core.h2h.weight', 'caption_model.core.attention.h2att.weight']
-            if not (self.cap_projected and self.opt['rnn_size'] <= 1024):
-                capk.append('caption_model.core.a2c.weight')     # (the projected-attention recurrence never multiplies by a2c^T row by row)
-        for k in (capk if self.var['cap'] is not None else []):
-            add(k, P.view(k), *P.shapes[k])
+        for k in (self.captioner.transposed_keys() if self.captioner is not None else []):
+            add('caption_model.' + k, P.view('caption_model.' + k), *P.shapes['caption_model.' + k])
         # (the dynamic-filter matrix, 7175 x 1024 fp32 = 29 MB, is read as stored by the split NN kernel: no copy)
         # 2x2 deconv: its forward operand [(dy,dx,co)][ci] is the transpose of the master [ci][(dy,dx,co)] (activation dtype)
         add('mask_up', P.view('mask_up_sampling.weight'), 2048, 4 * 256, dst=self.up_wT, f32=0)
@@ -324,442 +317,17 @@ class resnetv1(Network):
         self.bwd_x(dx, 'rnn_encoder.mlp.0.weight', demb, T)
         O.embed_bwd(demb, t['enc.emb'], d['labels'], t['enc.drop'], P.view('rnn_encoder.embedding.weight', P.grad), T, E, False)
 
-    # ------------------------------------------------------------------ head and tail of both captioners (ATT:60-101; CRIT:43-53)
-    def _cap_head_fwd(self, pre, att_feats):
-        """att_embed (Linear + ReLU on the 196 attention features) -> attention dropout -> ctx2att: (ad [196][rnn_size], patt [196][att_hid_size])"""
-        t = self.t
-        R, AH, L = self.opt['rnn_size'], self.opt['att_hid_size'], 196
-        a = self.buf('cap.a', (L, R), f32)
-        self.att_embed.fwd(att_feats, L, 1, 1, a, relu=True, out_f32=True)
-        t['cap.a_pre'], t['cap.drop_att'] = a, pre['drop_att']
-        if pre['drop_att'] is not None:
-            ad = self.buf('cap.ad', (L, R), f32); O.mul(a, pre['drop_att'], ad)
-        else:
-            ad = a
-        patt = self.buf('cap.patt', (L, AH), f32)
-        O.linear_fwd(ad, self.P.view('caption_model.ctx2att.weight'), self.P.view('caption_model.ctx2att.bias'), patt, L, AH, R)
-        return ad, patt
-
-    def _cap_tail_fwd(self, d, pre, h, ad, patt, loss):
-        """the recurrence's outputs h [S][rnn_size] -> output dropout -> logits -> log-softmax + masked NLL into loss[5]"""
-        t, S = self.t, d['S']
-        R, V1 = self.opt['rnn_size'], self.opt['vocab_size'] + 1
-        t['cap.drop_out'] = pre['drop_out']
-        if pre['drop_out'] is not None:
-            ho = self.buf('cap.ho', (S, R), f32); O.mul(h, pre['drop_out'], ho)
-        else:
-            ho = h
-        logits = self.buf('cap.logits', (S, V1), f32)
-        O.linear_fwd(ho, self.P.view('caption_model.logit.weight'), self.P.view('caption_model.logit.bias'), logits, S, V1, R)
-        dlogits = self.buf('cap.dlogits', (S, V1), f32)
-        lp = self.buf('cap.logp', (S, V1), f32) if self.keep_logprobs else None
-        O.logsoftmax_nll(logits, d['cap_tgt'], d['cap_mask'], S, V1, self._cap_loss_weight, loss[5:6], dlogits, lp)
-        t.update({'cap.ad': ad, 'cap.patt': patt, 'cap.xt': pre['xt'], 'cap.drop_xt': pre['drop_xt'], 'cap.ho': ho, 'cap.dlogits': dlogits, 'cap.logp': lp})
-
-    def _cap_head_bwd(self, S):
-        """-> (later, dho).  Only d(att_feats) is on the step's critical path (the main queue waits for it at the caption join): the parameter
-        gradients that nothing downstream reads are collected in `later` and issued after the branch has produced its result (caption_branch:
-        on the language stream, behind the join point); the logit layer's is the first.  dho [S][rnn_size]: d(outputs of the recurrence)"""
-        t = self.t
-        R, V1 = self.opt['rnn_size'], self.opt['vocab_size'] + 1
-        gv = lambda k: self.P.view('caption_model.' + k, self.P.grad)
-        dlogits = t['cap.dlogits']
-        later = self._cap_deferred = []
-        later.append(lambda: O.linear_bwd_w(dlogits, t['cap.ho'], gv('logit.weight'), gv('logit.bias'), S, V1, R))
-        dho = self.buf('cap.dho', (S, R), f32)
-        self.bwd_x(dlogits, 'caption_model.logit.weight', dho, S, mul=t['cap.drop_out'])
-        return later, dho
-
-    def _cap_tail_bwd(self, dad, att_feats):
-        """d(ad) [196][rnn_size], complete -> d(att_feats) in the activation dtype [196][att_feat_size] through att_embed"""
-        t = self.t
-        R, L = self.opt['rnn_size'], 196
-        dadT = self.buf('cap.dadT', (L, R))
-        # dropout mask (it multiplies the accumulated sum, not only this term), ReLU backward and the cast to the activation dtype: one launch
-        O.mask_relu_cast(dad, t['cap.drop_att'], t['cap.a_pre'], dadT)
-        self.att_embed.wgrad(dadT, att_feats, L, 1, 1)
-        datt = self.buf('cap.datt_feats', (L, self.opt['att_feat_size']))
-        self.att_embed.dgrad(dadT, L, 1, 1, datt)
-        return datt
-
-    # ------------------------------------------------------------------ att2in2 captioner (ATT:406-466)
-    # states live in (S+1)-row arrays, row 0 = zeros: h(i) = row i+1, h(i-1) = row i.
+    # ------------------------------------------------------------------ the captioner (--caption_model; nets/captioners.py)
     def _caption_pre(self, d):
         """token-only part of _caption_fwd / _caption_bwd, issued early on the language stream"""
-        if self.cap_model == 'topdown':
-            return self._topdown_pre(d)
-        if self.cap_model in ADAATT_GATES:
-            return self._adaatt_pre(d)
-        P, S = self.P, d['S']
-        R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
-        pv = lambda k: P.view('caption_model.' + k)
-        pre = {'drop_att': self._drop('att', (L, R), self.opt['drop_prob_lm']), 'drop_xt': self._drop('xt', (S, IE), self.opt['drop_prob_lm']),
-               'drop_out': self._drop('out', (S, R), self.opt['drop_prob_lm'])}
-        xt = self.buf('cap.xt', (S, IE), f32)
-        O.embed_fwd(pv('embed.0.weight'), d['cap_in'], pre['drop_xt'], xt, S, IE, True)
-        sums = self.buf('cap.sums', (S, 5 * R), f32)
-        O.linear_fwd(xt, pv('core.i2h.weight'), pv('core.i2h.bias'), sums, S, 5 * R, IE)
-        proj = self.cap_projected and R <= 1024
-        nz = L * AH + L * R + 4 * R
-        self.buf('cap.bwd_zero', (nz + (L * 2 * R if proj else 0),), f32, zero=True)
-        pre.update(xt=xt, sums=sums, zeroed=True)
-        return pre
+        return self.captioner.pre(d)
 
     def _caption_fwd(self, d, att_feats, loss):
-        if self.cap_model == 'topdown':
-            return self._topdown_fwd(d, att_feats, loss)
-        if self.cap_model in ADAATT_GATES:
-            return self._adaatt_fwd(d, att_feats, loss)
-        P, t, S = self.P, self.t, d['S']
-        pre = getattr(self, '_cap_pre', None) or self._caption_pre(d)
-        R, AH, L = self.opt['rnn_size'], self.opt['att_hid_size'], 196
-        SC = 256                                             # per-row scratch tail of the attention kernels
-        pv = lambda k: P.view('caption_model.' + k)
-        ad, patt = self._cap_head_fwd(pre, att_feats)
-        sums = pre['sums']
-        hs = self.buf('cap.hfull', (S + 1, R), f32); cs = self.buf('cap.cfull', (S + 1, R), f32); save = self.buf('cap.save', (S, 6 * R), f32)
-        att_h = self.buf('cap.att_h', (S, AH), f32); tanh_ws = self.buf('cap.tanh', (S, L, AH), f32)
-        wgt = self.buf('cap.wgt', (S, L), f32); ares = self.buf('cap.ares', (S, R + SC), f32); a2c = self.buf('cap.a2c', (S, 2 * R), f32)
-        proj = self.cap_projected and R <= 1024
-        if proj:
-            # projected attention (csrc/caption_step.hip): P = att . W_a2c^T once, then 3 launches per token
-            Pm = self.buf('cap.P', (L, 2 * R), f32); dots = self.buf('cap.dots', (S, 256), f32)
-            O.linear_fwd(ad, pv('core.a2c.weight'), None, Pm, L, 2 * R, R)
-            t['cap.P'] = Pm
-        t['cap.resident'] = resident = proj and self.cap_persistent and O.cap_recur_supported(S, R, AH, L)
-        if resident:
-            # the whole recurrence as one resident launch (csrc/cap_recur.hip): 32 workgroups own 16 units each, three granule exchanges per token
-            if getattr(self, '_cap_state', None) is None:
-                self._cap_state = (O.cap_recur_state(False), O.cap_recur_state(True))
-            O.cap_recur_fwd(pv('core.h2h.weight'), pv('core.h2h.bias'), pv('core.attention.h2att.weight'), pv('core.attention.h2att.bias'), patt,
-                            pv('core.attention.alpha_net.weight'), pv('core.attention.alpha_net.bias'), Pm, pv('core.a2c.bias'), sums, hs, cs, save,
-                            tanh_ws, wgt, self._cap_state[0], S, R, AH, L)
-        for i in range(0 if resident else S):
-            # h2att(h) and h2h(h) (+= i2h sums) in one launch; attention; a2c Linear fused with the gates (4 launches per step)
-            O.linear2_fwd(hs[i], R, pv('core.attention.h2att.weight'), pv('core.attention.h2att.bias'), att_h[i], AH, False,
-                          pv('core.h2h.weight'), pv('core.h2h.bias'), sums[i], 5 * R, True)
-            if proj:
-                O.cap_att_dots_fwd(patt, att_h[i], pv('core.attention.alpha_net.weight'), pv('core.attention.alpha_net.bias'), L, AH, tanh_ws[i], dots[i])
-                O.cap_apply_gates_fwd(Pm, dots[i], pv('core.a2c.bias'), sums[i], cs[i], cs[i + 1], hs[i + 1], save[i], wgt[i], L, R)
-                continue
-            O.cap_attention_fwd(patt, ad, att_h[i], pv('core.attention.alpha_net.weight'), pv('core.attention.alpha_net.bias'), L, AH,
-                                tanh_ws[i], wgt[i], ares[i])
-            O.cap_a2c_gates_fwd(ares[i], pv('core.a2c.weight'), pv('core.a2c.bias'), R, sums[i], cs[i], cs[i + 1], hs[i + 1], save[i], R)
-        self._cap_tail_fwd(d, pre, hs[1:], ad, patt, loss)
-        t['cap.zeroed'] = pre.get('zeroed')
+        return self.captioner.fwd(d, att_feats, loss)
 
     def _caption_bwd(self, d, att_feats):
-        """returns d(att_feats) in the activation dtype [196][att_feat_size]."""
-        if self.cap_model == 'topdown':
-            return self._topdown_bwd(d, att_feats)
-        if self.cap_model in ADAATT_GATES:
-            return self._adaatt_bwd(d, att_feats)
-        P, t, S = self.P, self.t, d['S']
-        R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
-        SC = 256
-        pv = lambda k: P.view('caption_model.' + k)
-        gv = lambda k: P.view('caption_model.' + k, P.grad)
-        hs = self.buf('cap.hfull', (S + 1, R), f32); cs = self.buf('cap.cfull', (S + 1, R), f32); save = self.buf('cap.save', (S, 6 * R), f32)
-        tanh_ws = self.buf('cap.tanh', (S, L, AH), f32); wgt = self.buf('cap.wgt', (S, L), f32)
-        ares = self.buf('cap.ares', (S, R + SC), f32)
-        ad = t['cap.ad']
-        later, dho = self._cap_head_bwd(S)
-        dsums = self.buf('cap.dsums', (S, 5 * R), f32); da2c = self.buf('cap.da2c', (S, 2 * R), f32)
-        datt_h = self.buf('cap.datt_h', (S, AH + SC), f32); dares = self.buf('cap.dares', (S, R), f32); ddot = self.buf('cap.ddot', (S, L), f32)
-        proj = self.cap_projected and R <= 1024
-        # dpatt | dad | dh | dc (| dP): one buffer, one clear
-        nz = L * AH + L * R + 4 * R
-        zb = self.buf('cap.bwd_zero', (nz + (L * 2 * R if proj else 0),), f32, zero=not t.get('cap.zeroed'))
-        dpatt = zb[:L * AH].view(L, AH); dad = zb[L * AH:L * AH + L * R].view(L, R)
-        dh = zb[L * AH + L * R:L * AH + L * R + 2 * R].view(2, R); dc = zb[L * AH + L * R + 2 * R:nz].view(2, R)
-        wT_h2h = self.wT['caption_model.core.h2h.weight'][0]; wT_h2att = self.wT['caption_model.core.attention.h2att.weight'][0]
-        k = 0
-        if proj:
-            Pm = t['cap.P']; dwl = self.buf('cap.dwl', (S, 256), f32); dP = zb[nz:].view(L, 2 * R)
-        if t.get('cap.resident'):
-            O.cap_recur_bwd(pv('core.h2h.weight'), pv('core.attention.h2att.weight'), Pm, pv('core.attention.alpha_net.weight'), save, cs, wgt, tanh_ws, dho,
-                            dsums, da2c, ddot, datt_h, self._cap_state[1], S, R, AH, L)
-        for i in range(-1 if t.get('cap.resident') else S - 1, -1, -1):
-            if proj:
-                # 3 launches per step: gates + d(weight) = P . d(a2c); softmax backward + datt_h; dh(i-1)
-                O.cap_gates_bwd_dw(dh[k], dc[k], save[i], cs[i], Pm, dsums[i], da2c[i], dc[1 - k], dwl[i], L, R, dh2=dho[i])
-                O.cap_attention_bwd_step2(dwl[i], tanh_ws[i], wgt[i], pv('core.attention.alpha_net.weight'), L, AH, ddot[i], datt_h[i])
-            else:
-                # 4 launches per step: gates (dh = recurrent part + this step's output gradient), a2c^T, the attention pieces the
-                # recurrence needs, and dh(i-1) = W_h2h^T dsums + W_h2att^T datt_h
-                O.cap_gates_bwd(dh[k], dc[k], save[i], cs[i], dsums[i], da2c[i], dc[1 - k], R, dh2=dho[i])
-                self.bwd_x(da2c[i], 'caption_model.core.a2c.weight', dares[i], 1)
-                O.cap_attention_bwd_step(dares[i], ad, tanh_ws[i], wgt[i], pv('core.attention.alpha_net.weight'), L, AH, ddot[i], datt_h[i])
-            O.linear_sum2_fwd(dsums[i], wT_h2h, 5 * R, datt_h[i], wT_h2att, AH, dh[1 - k], R)
-            k = 1 - k
-        O.cap_attention_bwd_batched(ddot, wgt, None if proj else dares, R, tanh_ws, pv('core.attention.alpha_net.weight'), S, L, AH, dpatt, dad,
-                                    gv('core.attention.alpha_net.weight'), gv('core.attention.alpha_net.bias'))
-        if proj:
-            # d(P) = sum_t weight_t (x) d(a2c)_t  [L][2R];  d(att) += d(P) . W_a2c
-            O.linear_bwd_w(wgt, da2c, dP, None, S, L, 2 * R)
-            self.bwd_x(dP, 'caption_model.core.a2c.weight', dad, L, accumulate=True)
-        hprev = hs[0:S]
-
-        def recurrence_grads():
-            if proj:
-                O.linear_bwd_w(dP, ad, gv('core.a2c.weight'), gv('core.a2c.bias'), L, 2 * R, R)
-            else:
-                O.linear_bwd_w(da2c, ares, gv('core.a2c.weight'), gv('core.a2c.bias'), S, 2 * R, R, ldx=R + SC)
-            O.linear_bwd_w(dsums, hprev, gv('core.h2h.weight'), gv('core.h2h.bias'), S, 5 * R, R)
-            O.linear_bwd_w(datt_h, hprev, gv('core.attention.h2att.weight'), gv('core.attention.h2att.bias'), S, AH, R, lddy=AH + SC)
-            O.linear_bwd_w(dsums, t['cap.xt'], gv('core.i2h.weight'), gv('core.i2h.bias'), S, 5 * R, IE)
-            dxt = self.buf('cap.dxt', (S, IE), f32)
-            self.bwd_x(dsums, 'caption_model.core.i2h.weight', dxt, S)
-            O.embed_bwd(dxt, t['cap.xt'], d['cap_in'], t['cap.drop_xt'], gv('embed.0.weight'), S, IE, True)
-            O.linear_bwd_w(dpatt, ad, gv('ctx2att.weight'), gv('ctx2att.bias'), L, AH, R)
-        later.append(recurrence_grads)
-        # ctx2att
-        self.bwd_x(dpatt, 'caption_model.ctx2att.weight', dad, L, accumulate=True)
-        return self._cap_tail_bwd(dad, att_feats)
-
-    # ------------------------------------------------------------------ top-down captioner (ATT:60-101,370-395,486-490; CRIT:43-53)
-    # Two nn.LSTMCell per token: att_lstm([h_lang(i-1); fc; xt_i]) -> attention(h_att(i)) -> lang_lstm([att_res; h_att(i)]); the output is
-    # h_lang(i).  Per-token launches only (csrc/caption_step.hip), 5 forward and 5 backward.  States live in (S+1)-row arrays whose row 0 stays
-    # zero: hl / cl / ca row i+1 = step i; `lin` row i+1 = [att_res(i) | h_att(i)], the language cell's input AND the attention cell's state.
-    def _topdown_pre(self, d):
-        """token-only part: dropout masks, word embedding, the xt columns of att_lstm.weight_ih for all S tokens, the zeroed backward buffer"""
-        P, S = self.P, d['S']
-        R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
-        pv = lambda k: P.view('caption_model.' + k)
-        p = self.opt['drop_prob_lm']
-        pre = {'drop_att': self._drop('att', (L, R), p), 'drop_fc': self._drop('fc', (R,), p), 'drop_xt': self._drop('xt', (S, IE), p),
-               'drop_out': self._drop('out', (S, R), p)}
-        xt = self.buf('cap.xt', (S, IE), f32)
-        O.embed_fwd(pv('embed.0.weight'), d['cap_in'], pre['drop_xt'], xt, S, IE, True)
-        Ka = IE + 2 * R
-        xpre = self.buf('td.xpre', (S, 4 * R), f32)
-        O.linear_fwd(xt, pv('core.att_lstm.weight_ih')[2 * R:], pv('core.att_lstm.bias_ih'), xpre, S, 4 * R, IE, ldw=Ka)
-        self.buf('td.bwd_zero', (L * AH + L * R + 4 * R,), f32, zero=True)          # dpatt | dad | sum over tokens of d(att gates)
-        pre.update(xt=xt, xpre=xpre, zeroed=True)
-        return pre
-
-    def _topdown_bufs(self, S):
-        R, AH, L = self.opt['rnn_size'], self.opt['att_hid_size'], 196
-        b = lambda n, shp: self.buf('td.' + n, shp, f32)
-        return dict(hl=b('hl', (S + 1, R)), cl=b('cl', (S + 1, R)), ca=b('ca', (S + 1, R)), lin=b('lin', (S + 1, 2 * R)), act_a=b('act_a', (S, 4 * R)),
-                    act_l=b('act_l', (S, 4 * R)), att_h=b('att_h', (S, AH)), tanh=b('tanh', (S, L, AH)), wgt=b('wgt', (S, L)), dots=b('dots', (S, 256)))
-
-    def _topdown_fwd(self, d, att_feats, loss):
-        P, t, S = self.P, self.t, d['S']
-        pre = getattr(self, '_cap_pre', None) or self._topdown_pre(d)
-        R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
-        FC, Ka = self.opt['fc_feat_size'], IE + 2 * R
-        pv = lambda k: P.view('caption_model.' + k)
-        ad, patt = self._cap_head_fwd(pre, att_feats)
-        # fc_embed = Linear + ReLU + dropout on the pooled [mean | masked mean] vector, then its columns of att_lstm.weight_ih (+ bias_hh): once
-        fc = t['fc_feats']
-        if fc.dtype != f32:
-            fc32 = self.buf('td.fc32', (FC,), f32); O.cast(fc, fc32)
-        else:
-            fc32 = fc
-        fce = self.buf('td.fce', (R,), f32)
-        O.linear_fwd(fc32, pv('fc_embed.0.weight'), pv('fc_embed.0.bias'), fce, 1, R, FC, act=1)
-        if pre['drop_fc'] is not None:
-            fcd = self.buf('td.fcd', (R,), f32); O.mul(fce, pre['drop_fc'], fcd)
-        else:
-            fcd = fce
-        fcrow = self.buf('td.fcrow', (4 * R,), f32)
-        O.linear_fwd(fcd, pv('core.att_lstm.weight_ih')[R:], pv('core.att_lstm.bias_hh'), fcrow, 1, 4 * R, R, ldw=Ka)
-        B = self._topdown_bufs(S)
-        hl, cl, ca, lin = B['hl'], B['cl'], B['ca'], B['lin']
-        wa_ih, wa_hh, wl_ih, wl_hh = pv('core.att_lstm.weight_ih'), pv('core.att_lstm.weight_hh'), pv('core.lang_lstm.weight_ih'), pv('core.lang_lstm.weight_hh')
-        bl_ih, bl_hh = pv('core.lang_lstm.bias_ih'), pv('core.lang_lstm.bias_hh')
-        h2w, h2b = pv('core.attention.h2att.weight'), pv('core.attention.h2att.bias')
-        aw, ab = pv('core.attention.alpha_net.weight'), pv('core.attention.alpha_net.bias')
-        xpre = pre['xpre']
-        for i in range(S):
-            h_att = lin[i + 1][R:]
-            O.topdown_cell_fwd(xpre[i], fcrow, None, [(hl[i], wa_ih, Ka, R), (lin[i][R:], wa_hh, R, R)], ca[i], ca[i + 1], h_att, B['act_a'][i], R)
-            O.linear_fwd(h_att, h2w, h2b, B['att_h'][i], 1, AH, R)
-            O.cap_att_dots_fwd(patt, B['att_h'][i], aw, ab, L, AH, B['tanh'][i], B['dots'][i])
-            O.cap_att_apply_fwd(ad, B['dots'][i], L, R, B['wgt'][i], lin[i + 1])
-            O.topdown_cell_fwd(None, bl_ih, bl_hh, [(lin[i + 1], wl_ih, 2 * R, 2 * R), (hl[i], wl_hh, R, R)], cl[i], cl[i + 1], hl[i + 1], B['act_l'][i], R)
-        self._cap_tail_fwd(d, pre, hl[1:], ad, patt, loss)
-        t.update({'td.fc32': fc32, 'td.fce': fce, 'td.fcd': fcd, 'td.drop_fc': pre['drop_fc'], 'td.zeroed': pre.get('zeroed')})
-
-    def _topdown_bwd(self, d, att_feats):
-        """returns d(att_feats) in the activation dtype [196][att_feat_size]; d(fc_feats) float [fc_feat_size] is left in self.t['cap.dfc']"""
-        P, t, S = self.P, self.t, d['S']
-        R, IE, AH, L = self.opt['rnn_size'], self.opt['input_encoding_size'], self.opt['att_hid_size'], 196
-        FC, Ka = self.opt['fc_feat_size'], IE + 2 * R
-        pv = lambda k: P.view('caption_model.' + k)
-        gv = lambda k: P.view('caption_model.' + k, P.grad)
-        wT = lambda k: self.wT['caption_model.' + k][0]
-        B = self._topdown_bufs(S)
-        hl, cl, ca, lin = B['hl'], B['cl'], B['ca'], B['lin']
-        ad = t['cap.ad']
-        later, dho = self._cap_head_bwd(S)
-        nz = L * AH + L * R + 4 * R
-        zb = self.buf('td.bwd_zero', (nz,), f32, zero=not t.get('td.zeroed'))
-        dpatt = zb[:L * AH].view(L, AH); dad = zb[L * AH:L * AH + L * R].view(L, R); dgsum = zb[L * AH + L * R:]
-        b = lambda n, shp: self.buf('td.' + n, shp, f32)
-        dga, dgl, dares, dwl = b('dga', (S, 4 * R)), b('dgl', (S, 4 * R)), b('dares', (S, R)), b('dwl', (S, 256))
-        ddot, datt_h, dca, dcl = b('ddot', (S, L)), b('datt_h', (S, AH)), b('dca', (2, R)), b('dcl', (2, R))
-        ta_ih, ta_hh, tl_ih, tl_hh, th2 = wT('core.att_lstm.weight_ih'), wT('core.att_lstm.weight_hh'), wT('core.lang_lstm.weight_ih'), \
-            wT('core.lang_lstm.weight_hh'), wT('core.attention.h2att.weight')
-        aw = pv('core.attention.alpha_net.weight')
-        G = 4 * R
-        k = 0
-        for i in range(S - 1, -1, -1):
-            last = i == S - 1
-            # language cell: dh = this token's output gradient + what the NEXT token's two cells read of h_lang(i)
-            O.topdown_cell_bwd([] if last else [(dga[i + 1], ta_ih, G, G), (dgl[i + 1], tl_hh, G, G)], dho[i], None, None if last else dcl[k],
-                               B['act_l'][i], cl[i], cl[i + 1], dgl[i], dcl[1 - k], R)
-            # attention: d(att_res) through the first R rows of lang_lstm.weight_ih^T, d(weight) = att . d(att_res), softmax backward + d(att_h)
-            O.linear_fwd(dgl[i], tl_ih, None, dares[i], 1, R, G)
-            O.linear_fwd(dares[i], ad, None, dwl[i], 1, L, R)
-            O.cap_att_bwd_step_centered(dwl[i], B['tanh'][i], B['wgt'][i], aw, L, AH, ddot[i], datt_h[i])
-            # attention cell: dh = the language cell's input + h2att + its own recurrence
-            O.topdown_cell_bwd([(dgl[i], tl_ih[R * G:], G, G), (datt_h[i], th2, AH, AH)] + ([] if last else [(dga[i + 1], ta_hh, G, G)]), None, None,
-                               None if last else dca[k], B['act_a'][i], ca[i], ca[i + 1], dga[i], dca[1 - k], R)
-            k = 1 - k
-        # everything the per-token launches left out of the attention, summed over the S tokens
-        # (alpha_net.bias shifts every score alike and the softmax does not see it: its gradient is 0, and what the launch adds up for it -
-        # sum ddot, pure rounding error - goes to a scratch word instead of the gradient buffer)
-        O.cap_attention_bwd_batched(ddot, B['wgt'], None, R, B['tanh'], aw, S, L, AH, dpatt, dad, gv('core.attention.alpha_net.weight'),
-                                    b('dab_unused', (1,)))
-        O.linear_bwd_w(B['wgt'], dares, dad, None, S, L, R)                     # d(att) += sum_t weight_t (x) d(att_res)_t
-        self.bwd_x(dpatt, 'caption_model.ctx2att.weight', dad, L, accumulate=True)
-        # d(fc_feats): the fc columns see every token's gate gradient, so their sum goes through the transposed block once
-        O.colsum(dga, S, G, G, dgsum)
-        dfcd = self.buf('td.dfcd', (R,), f32)
-        O.linear_fwd(dgsum, ta_ih[R * G:], None, dfcd, 1, R, G)
-        if t['td.drop_fc'] is not None:
-            O.mul(dfcd, t['td.drop_fc'], dfcd)
-        O.act_bwd(dfcd, t['td.fce'], 1)
-        dfc = self.buf('td.dfc', (FC,), f32)
-        self.bwd_x(dfcd, 'caption_model.fc_embed.0.weight', dfc, 1)
-        t['cap.dfc'] = dfc
-
-        def recurrence_grads():
-            # the attention cell's input rows [h_lang(i-1) | fc | xt_i], packed once: its weight gradient is ONE product
-            X = self.buf('td.xatt', (S, Ka), f32, zero=True)
-            if S > 1:
-                O.pack_rows(X[1:], Ka, hl[1:], R, S - 1, R)
-            O.pack_rows(X[:, R:], Ka, t['td.fcd'], 0, S, R)
-            O.pack_rows(X[:, 2 * R:], Ka, t['cap.xt'], IE, S, IE)
-            O.linear_bwd_w(dga, X, gv('core.att_lstm.weight_ih'), gv('core.att_lstm.bias_ih'), S, G, Ka)
-            O.linear_bwd_w(dga, lin[:, R:], gv('core.att_lstm.weight_hh'), gv('core.att_lstm.bias_hh'), S, G, R, ldx=2 * R)
-            O.linear_bwd_w(dgl, lin[1:], gv('core.lang_lstm.weight_ih'), gv('core.lang_lstm.bias_ih'), S, G, 2 * R)
-            O.linear_bwd_w(dgl, hl, gv('core.lang_lstm.weight_hh'), gv('core.lang_lstm.bias_hh'), S, G, R)
-            O.linear_bwd_w(datt_h, lin[1:, R:], gv('core.attention.h2att.weight'), gv('core.attention.h2att.bias'), S, AH, R, ldx=2 * R)
-            O.linear_bwd_w(dfcd, t['td.fc32'], gv('fc_embed.0.weight'), gv('fc_embed.0.bias'), 1, R, FC)
-            dxt = self.buf('cap.dxt', (S, IE), f32)
-            dX = self.buf('td.dxatt', (S, Ka), f32)
-            self.bwd_x(dga, 'caption_model.core.att_lstm.weight_ih', dX, S)
-            O.pack_rows(dxt, IE, dX[:, 2 * R:], Ka, S, IE)
-            O.embed_bwd(dxt, t['cap.xt'], d['cap_in'], t['cap.drop_xt'], gv('embed.0.weight'), S, IE, True)
-            # ctx2att.bias enters the tanh like h2att's output: its gradient is sum_t datt_h[t], whose sum over the locations was taken in the
-            # well-conditioned form; the column sums of dpatt would add that sum's rounding error back
-            O.linear_bwd_w(dpatt, ad, gv('ctx2att.weight'), None, L, AH, R)
-            O.colsum(datt_h, S, AH, AH, gv('ctx2att.bias'))
-        later.append(recurrence_grads)
-        datt = t['cap.datt'] = self._cap_tail_bwd(dad, att_feats)
-        return datt
-
-    # ------------------------------------------------------------------ adaptive-attention captioners (ATT:211-368,468-477; adaatt / adaattmo)
-    # An LSTM with a sentinel gate, then an additive attention over the 196 locations + the sentinel.  Only the cell is recurrent: one launch per
-    # token each way; the attention runs once for all tokens (nets/adaatt.py has the sequence, csrc/adaatt_step.hip the kernels).
-    def _adaatt_masks(self, pre):
-        return {k: pre['drop_' + k] for k in ('toph', 'fake', 'frl', 'hol', 'hA')}
-
-    def _adaatt_pre(self, d):
-        """token-only part: dropout masks, word embedding, w2h(xt) | r_w2h(xt) for all S tokens, the zeroed backward buffer"""
-        P, S = self.P, d['S']
-        R, IE, L, G = self.opt['rnn_size'], self.opt['input_encoding_size'], 196, ADAATT_GATES[self.cap_model]
-        pv = lambda k: P.view('caption_model.' + k)
-        p = self.opt['drop_prob_lm']
-        pre = {'drop_att': self._drop('att', (L, R), p), 'drop_fc': self._drop('fc', (R,), p), 'drop_xt': self._drop('xt', (S, IE), p),
-               'drop_out': self._drop('out', (S, R), p), 'drop_hA': self._drop('hA', (S, L + 1, R), p)}
-        for k in ('toph', 'fake', 'frl', 'hol'):
-            pre['drop_' + k] = self._drop(k, (S, R), p)
-        xt = self.buf('cap.xt', (S, IE), f32)
-        O.embed_fwd(pv('embed.0.weight'), d['cap_in'], pre['drop_xt'], xt, S, IE, True)
-        W = (G + 1) * R
-        xpre = self.buf('ada.xpre', (S, W), f32)
-        O.linear_fwd(xt, pv('core.lstm.w2h.weight'), pv('core.lstm.w2h.bias'), xpre, S, G * R, IE, ldy=W)
-        O.linear_fwd(xt, pv('core.lstm.r_w2h.weight'), pv('core.lstm.r_w2h.bias'), xpre[:, G * R:], S, R, IE, ldy=W)
-        self.buf('ada.bwd_zero', (2 * L * R + W,), f32, zero=True)                 # dpatt | dad | sum over tokens of d(sums | n5)
-        pre.update(xt=xt, xpre=xpre, zeroed=True)
-        return pre
-
-    def _adaatt_fwd(self, d, att_feats, loss):
-        from . import adaatt as AA
-        P, t, S = self.P, self.t, d['S']
-        pre = getattr(self, '_cap_pre', None) or self._adaatt_pre(d)
-        R, L, G = self.opt['rnn_size'], 196, ADAATT_GATES[self.cap_model]
-        FC = self.opt['fc_feat_size']
-        pv = lambda k: P.view('caption_model.' + k)
-        ad, patt = self._cap_head_fwd(pre, att_feats)
-        # fc_embed = Linear + ReLU + dropout on the pooled vector, then v2h | r_v2h of it: once per sentence
-        fc = t['fc_feats']
-        if fc.dtype != f32:
-            fc32 = self.buf('ada.fc32', (FC,), f32); O.cast(fc, fc32)
-        else:
-            fc32 = fc
-        fce = self.buf('ada.fce', (R,), f32)
-        O.linear_fwd(fc32, pv('fc_embed.0.weight'), pv('fc_embed.0.bias'), fce, 1, R, FC, act=1)
-        if pre['drop_fc'] is not None:
-            fcd = self.buf('ada.fcd', (R,), f32); O.mul(fce, pre['drop_fc'], fcd)
-        else:
-            fcd = fce
-        fcrow = self.buf('ada.fcrow', ((G + 1) * R,), f32)
-        O.linear_fwd(fcd, pv('core.lstm.v2h.weight'), pv('core.lstm.v2h.bias'), fcrow, 1, G * R, R)
-        O.linear_fwd(fcd, pv('core.lstm.r_v2h.weight'), pv('core.lstm.r_v2h.bias'), fcrow[G * R:], 1, R, R)
-        B = {k: self.buf('ada.' + k, shp, f32) for k, shp in AA.fwd_shapes(S, L, R).items()}
-        V = AA.core_fwd(O, lambda k: pv('core.' + k), B, pre['xpre'], fcrow, ad, patt, self._adaatt_masks(pre), S, L, R, G)
-        self._cap_tail_fwd(d, pre, B['outs'], ad, patt, loss)
-        t.update({'ada.fc32': fc32, 'ada.fce': fce, 'ada.fcd': fcd, 'ada.pre': pre, 'ada.B': B, 'ada.V': V, 'ada.zeroed': pre.get('zeroed')})
-
-    def _adaatt_bwd(self, d, att_feats):
-        """returns d(att_feats) in the activation dtype [196][att_feat_size]; d(fc_feats) float [fc_feat_size] is left in self.t['cap.dfc']"""
-        from . import adaatt as AA
-        P, t, S = self.P, self.t, d['S']
-        R, IE, L, G = self.opt['rnn_size'], self.opt['input_encoding_size'], 196, ADAATT_GATES[self.cap_model]
-        FC, W = self.opt['fc_feat_size'], (G + 1) * R
-        pv = lambda k: P.view('caption_model.core.' + k)
-        gv = lambda k: P.view('caption_model.' + k, P.grad)
-        B, V, masks = t['ada.B'], t['ada.V'], self._adaatt_masks(t['ada.pre'])
-        ad = t['cap.ad']
-        later, dho = self._cap_head_bwd(S)
-        zb = self.buf('ada.bwd_zero', (2 * L * R + W,), f32, zero=not t.get('ada.zeroed'))
-        dpatt = zb[:L * R].view(L, R); dad = zb[L * R:2 * L * R].view(L, R); dgsum = zb[2 * L * R:]
-        D = {k: self.buf('ada.' + k, shp, f32) for k, shp in AA.bwd_shapes(S, L, R, G).items()}
-        wT = (self.wT['caption_model.core.lstm.h2h.0.weight'][0], self.wT['caption_model.core.lstm.r_h2h.weight'][0])
-        bwd_x = lambda dy, k, dx, M, **kw: self.bwd_x(dy, 'caption_model.core.' + k, dx, M, **kw)
-        AA.core_bwd(O, pv, wT, bwd_x, B, D, V, dho, ad, dpatt, dad, gv('core.attention.alpha_net.weight'), masks, S, L, R, G)
-        # d(fc_feats): v2h | r_v2h see every token's gradient, so their sum goes through the two matrices once
-        O.colsum(D['dall'], S, W, W, dgsum)
-        dfcd = self.buf('ada.dfcd', (R,), f32)
-        bwd_x(dgsum, 'lstm.v2h.weight', dfcd, 1)
-        bwd_x(dgsum[G * R:], 'lstm.r_v2h.weight', dfcd, 1, accumulate=True)
-        if t['ada.pre']['drop_fc'] is not None:
-            O.mul(dfcd, t['ada.pre']['drop_fc'], dfcd)
-        O.act_bwd(dfcd, t['ada.fce'], 1)
-        dfc = self.buf('ada.dfc', (FC,), f32)
-        self.bwd_x(dfcd, 'caption_model.fc_embed.0.weight', dfc, 1)
-        t['cap.dfc'] = dfc
-        self.bwd_x(dpatt, 'caption_model.ctx2att.weight', dad, L, accumulate=True)
-
-        def recurrence_grads():
-            AA.core_wgrads(O, lambda k: gv('core.' + k), B, D, V, dho, t['cap.xt'], t['ada.fcd'], dgsum, S, R, IE, G)
-            O.linear_bwd_w(dfcd, t['ada.fc32'], gv('fc_embed.0.weight'), gv('fc_embed.0.bias'), 1, R, FC)
-            dxt = self.buf('cap.dxt', (S, IE), f32)
-            bwd_x(D['dall'], 'lstm.w2h.weight', dxt, S, lddy=W)
-            bwd_x(D['dall'][:, G * R:], 'lstm.r_w2h.weight', dxt, S, accumulate=True, lddy=W)
-            O.embed_bwd(dxt, t['cap.xt'], d['cap_in'], t['cap.drop_xt'], gv('embed.0.weight'), S, IE, True)
-            # ctx2att.bias: the sum over the LOCATIONS of what enters the tanh, taken in the well-conditioned form by the step kernel (dctx);
-            # the column sums of dpatt would add that sum's rounding error back (as for the top-down captioner)
-            O.linear_bwd_w(dpatt, ad, gv('ctx2att.weight'), None, L, R, R)
-            O.colsum(D['dctx'], S, R, R, gv('ctx2att.bias'))
-        later.append(recurrence_grads)
-        datt = t['cap.datt'] = self._cap_tail_bwd(dad, att_feats)
-        return datt
+        """returns d(att_feats) in the activation dtype [196][att_feat_size]; a captioner that reads fc_feats leaves d(fc_feats) in self.t['cap.dfc']"""
+        return self.captioner.bwd(d, att_feats)
 
     # ------------------------------------------------------------------ backbone / RoI-head hooks (overridden by the VGG variant)
     def _backbone_fwd(self, d, saved):
@@ -1147,13 +715,6 @@ class resnetv1(Network):
         # and rejoins at d(net_conv); layer4's weight gradients from both branches accumulate atomically.
         AF = self.opt['att_feat_size']
 
-        def l4_on_map(xin, tag):
-            x, hh, ww = xin, Hc, Wc
-            for b, blk in enumerate(self.layers[4]):
-                x, hh, ww, sv = blk.fwd(x, 1, hh, ww, '%s.%d' % (tag, b))
-                saved[(tag, b)] = sv
-            return x
-
         def l4_on_map_bwd(g, tag, in_relu=False):
             # in_relu: the map that was fed in is itself a ReLU output (layer3's), so its gradient is masked here
             self.prio_floor = self.cap_map_prio
@@ -1169,35 +730,20 @@ class resnetv1(Network):
             if 'cap' in self.knockout:
                 return self.buf('l4m.skip', (HW, C4)), None
             self._mark('dyn fwd')
-            feats = l4_on_map(net_conv, 'l4m')
+            feats = self._l4_on_map(net_conv, Hc, Wc, 'l4m', saved)
             self._mark('cap: layer4 on map fwd')
-            att = self.buf('cap.att', (196, AF))
-            topdown = self.cap_model in FC_CAPTIONERS        # the captioner reads fc_feats (top-down and the AdaAtt pair)
-            if topdown:
-                FC = self.opt['fc_feat_size']
-                if FC != 2 * 2048:
-                    raise ValueError('fc_feat_size %r: fc_feats is the pair of 2048-channel means of layer4 on the map (4096)' % (FC,))
-                fc = t['fc_feats'] = self.buf('cap.fc', (FC,))
             if self.var['cap'] == 'mask':
                 gm = self.buf('cap.gm', (HW,), f32)
                 O.mask_downsample(d['gt_masks'], gm, H, W, Hc, Wc)
-                O.adaptive_pool_fwd(feats, None, att, Hc, Wc, 2048, 14, 14, AF)
-                O.adaptive_pool_fwd(feats, gm, att[:, 2048:], Hc, Wc, 2048, 14, 14, AF)
+                att, fc = self._caption_pools([(feats, None), (feats, gm)], Hc, Wc)
                 t.update({'feats_all': feats, 'att_feats': att, 'gt_mask_small': gm})
-                if topdown:
-                    # fc_feats = [mean of the map | mean of the masked map] (NET:418,431,434): the same pooling with ONE output bin
-                    O.adaptive_pool_fwd(feats, None, fc, Hc, Wc, 2048, 1, 1, FC)
-                    O.adaptive_pool_fwd(feats, gm, fc[2048:], Hc, Wc, 2048, 1, 1, FC)
             else:
-                # cycle_response: [layer4(map before the gating) ; layer4(gated map)] (network_cycle_response.py:425-439)
-                feats_b = l4_on_map(base, 'l4b')
-                O.adaptive_pool_fwd(feats_b, None, att, Hc, Wc, 2048, 14, 14, AF)
-                O.adaptive_pool_fwd(feats, None, att[:, 2048:], Hc, Wc, 2048, 14, 14, AF)
+                feats_b = self._l4_on_map(base, Hc, Wc, 'l4b', saved)
+                att, fc = self._caption_pools([(feats_b, None), (feats, None)], Hc, Wc)
                 t.update({'feats_all': feats, 'feats_before_all': feats_b, 'att_feats': att})
-                if topdown:
-                    # fc_feats = [mean before the gating | mean after] (network_cycle_response.py:428,431,438)
-                    O.adaptive_pool_fwd(feats_b, None, fc, Hc, Wc, 2048, 1, 1, FC)
-                    O.adaptive_pool_fwd(feats, None, fc[2048:], Hc, Wc, 2048, 1, 1, FC)
+            reads_fc, FC = fc is not None, self.opt.get('fc_feat_size')
+            if reads_fc:
+                t['fc_feats'] = fc
             self._mark('cap: pools')
             yield
             self._caption_fwd(d, att, loss)
@@ -1228,7 +774,7 @@ class resnetv1(Network):
                 return dfc
             if self.var['cap'] == 'mask':
                 O.adaptive_pool_bwd(datt, AF, 0, 2048, gm, g, feats, Hc, Wc, 2048, 14, 14)
-                if topdown:
+                if reads_fc:
                     # d(fc_feats) joins d(feats) before layer4's data gradient: the one-bin pooling backward, added to the 14x14 one
                     dfc, g2 = fc_grad(), self.buf('l4m.gfc', (HW, 2048))
                     O.adaptive_pool_bwd(dfc, FC, 0, 2048, gm, g2, feats, Hc, Wc, 2048, 1, 1)
@@ -1240,7 +786,7 @@ class resnetv1(Network):
             gb = self.buf('l4b.g', (HW, 2048))
             O.adaptive_pool_bwd(datt, AF, 0, 0, None, gb, feats_b, Hc, Wc, 2048, 14, 14)
             O.adaptive_pool_bwd(datt, AF, 2048, 0, None, g, feats, Hc, Wc, 2048, 14, 14)
-            if topdown:
+            if reads_fc:
                 dfc, g2 = fc_grad(), self.buf('l4m.gfc', (HW, 2048))
                 O.adaptive_pool_bwd(dfc, FC, 0, 0, None, g2, feats_b, Hc, Wc, 2048, 1, 1)
                 O.add3(gb, g2, None, gb)
@@ -1526,6 +1072,31 @@ class resnetv1(Network):
             self._cst = dict(means=mk(TR.BBOX_NORMALIZE_MEANS), stds=mk(TR.BBOX_NORMALIZE_STDS), inw=mk(TR.BBOX_INSIDE_WEIGHTS))
         return self._cst
 
+    def _l4_on_map(self, x, h, w, tag, saved=None):
+        """layer4 on a whole map [h * w][1024] as one RoI of its size -> [h * w][2048]; saved: where backward finds what each block kept"""
+        for b, blk in enumerate(self.layers[4]):
+            x, h, w, sv = blk.fwd(x, 1, h, w, '%s.%d' % (tag, b))
+            if saved is not None:
+                saved[(tag, b)] = sv
+        return x
+
+    def _caption_pools(self, halves, Hc, Wc):
+        """(att_feats [196][att_feat_size], fc_feats [fc_feat_size] or None: for a captioner that reads it) of the train branch and of
+        caption_features.  halves: the two (layer4 on a map, mask at the map's size or None) whose 2048 pooled channels make up each row -
+        cycle: [the map | the map under the mask] (NET:418,431,434); cycle_response: [the map before the gating | the gated map]
+        (network_cycle_response.py:425-439).  att_feats pools 14 x 14 bins, fc_feats the same with ONE bin: the mean"""
+        AF, FC = self.opt['att_feat_size'], self.opt.get('fc_feat_size')
+        att, fc = self.buf('cap.att', (196, AF)), None
+        for j, (x, m) in enumerate(halves):
+            O.adaptive_pool_fwd(x, m, att[:, 2048 * j:], Hc, Wc, 2048, 14, 14, AF)
+        if self.captioner.reads_fc:
+            if FC != 2 * 2048:
+                raise ValueError('fc_feat_size %r: fc_feats is the pair of 2048-channel means of layer4 on the map (4096)' % (FC,))
+            fc = self.buf('cap.fc', (FC,))
+            for j, (x, m) in enumerate(halves):
+                O.adaptive_pool_fwd(x, m, fc[2048 * j:], Hc, Wc, 2048, 1, 1, FC)
+        return att, fc
+
     # ------------------------------------------------------------------ mask -> sentence (AttModel.py:103-209, CaptionModel.py:23-124)
     def caption_features(self, mask_u8=None):
         """(att_feats [196][att_feat_size], fc_feats [fc_feat_size] or None) of the sentence whose TEST forward ran last (forward_test_sentence),
@@ -1537,42 +1108,16 @@ class resnetv1(Network):
         if p is None:
             raise RuntimeError('caption_features follows forward_test_sentence: no TEST forward has run')
         net_conv, (Hc, Wc), (H, W) = p['net_conv'], p['net_conv_hw'], p['blob_hw']
-        AF = self.opt['att_feat_size']
-
-        def l4_on_map(x, tag):
-            hh, ww = Hc, Wc
-            for b, blk in enumerate(self.layers[4]):
-                x, hh, ww, _ = blk.fwd(x, 1, hh, ww, '%s.%d' % (tag, b))
-            return x
-        feats = l4_on_map(net_conv, 'l4m')
-        att = self.buf('cap.att', (196, AF))
-        fc = None
-        if self.cap_model in FC_CAPTIONERS:
-            FC = self.opt['fc_feat_size']
-            if FC != 2 * 2048:
-                raise ValueError('fc_feat_size %r: fc_feats is the pair of 2048-channel means of layer4 on the map (4096)' % (FC,))
-            fc = self.buf('cap.fc', (FC,))
+        feats = self._l4_on_map(net_conv, Hc, Wc, 'l4m')
         if self.var['cap'] == 'mask':
             if mask_u8 is None or mask_u8.dtype != torch.uint8 or mask_u8.numel() != H * W:
                 raise ValueError('caption_features: the cycle network pools under a uint8 mask of the blob\'s size %d x %d' % (H, W))
             gm = self.buf('cap.gm', (Hc * Wc,), f32)
             O.mask_downsample(mask_u8, gm, H, W, Hc, Wc)
-            O.adaptive_pool_fwd(feats, None, att, Hc, Wc, 2048, 14, 14, AF)
-            O.adaptive_pool_fwd(feats, gm, att[:, 2048:], Hc, Wc, 2048, 14, 14, AF)
-            if fc is not None:
-                O.adaptive_pool_fwd(feats, None, fc, Hc, Wc, 2048, 1, 1, FC)
-                O.adaptive_pool_fwd(feats, gm, fc[2048:], Hc, Wc, 2048, 1, 1, FC)
-        else:
-            feats_b = l4_on_map(p['base'], 'l4b')
-            O.adaptive_pool_fwd(feats_b, None, att, Hc, Wc, 2048, 14, 14, AF)
-            O.adaptive_pool_fwd(feats, None, att[:, 2048:], Hc, Wc, 2048, 14, 14, AF)
-            if fc is not None:
-                O.adaptive_pool_fwd(feats_b, None, fc, Hc, Wc, 2048, 1, 1, FC)
-                O.adaptive_pool_fwd(feats, None, fc[2048:], Hc, Wc, 2048, 1, 1, FC)
-        return att, fc
+            return self._caption_pools([(feats, None), (feats, gm)], Hc, Wc)
+        return self._caption_pools([(self._l4_on_map(p['base'], Hc, Wc, 'l4b'), None), (feats, None)], Hc, Wc)
 
     def caption_decode(self, att_feats, fc_feats=None, sample_max=1, beam_size=1, temperature=1.0):
         """greedy (sample_max = 1), sampled (sample_max = 0, temperature) or beam-search (beam_size > 1) decoding of the selected captioner on
         the device, eval mode: {'seq', 'logprobs'} (+ 'beams' for beam search).  nets/decode.py"""
-        from . import decode
         return decode.caption_decode(self, att_feats, fc_feats, sample_max, beam_size, temperature)

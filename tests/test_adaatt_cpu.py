@@ -213,7 +213,7 @@ def test_tools_accept_the_option(model):
 @pytest.mark.parametrize('S,masks', [(1, False), (3, False), (3, True)])
 @pytest.mark.parametrize('model', MODELS)
 def test_captioner_host_order_with_torch_kernels(model, S, masks, monkeypatch):
-    """Network._adaatt_pre / _adaatt_fwd / _adaatt_bwd with every entry point they call restated in torch (adaatt_util.TorchOps): the host's
+    """nets/captioners.py AdaAtt (pre / fwd / bwd through Network._caption_*) with every entry point it calls restated in torch (adaatt_util.TorchOps): the host's
     part - which buffer, column block, transposed copy and key goes into which launch, in which order - gives the restatement's
     log-probabilities, loss, parameter gradients and d(att_feats) / d(fc_feats), with the nine injected dropout masks and without"""
     from lang2seg_amd import ops as O

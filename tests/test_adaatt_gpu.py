@@ -1,5 +1,5 @@
-"""The adaptive-attention captioners on the device (csrc/adaatt_step.hip, nets/adaatt.py and nets/resnet_v1.py _adaatt_pre / _adaatt_fwd /
-_adaatt_bwd) against the torch restatement of tests/adaatt_util.py, which tests/test_adaatt_cpu.py pins to the reference's own models.
+"""The adaptive-attention captioners on the device (csrc/adaatt_step.hip, nets/adaatt.py and nets/captioners.py AdaAtt) against the torch
+restatement of tests/adaatt_util.py, which tests/test_adaatt_cpu.py pins to the reference's own models.
 Bounds: the kernel family's (tests/test_kernels_gpu.py rel_err) 1e-5 forward and 1e-4 gradients; 1e-4 on losses in exact-f32 mode; bf16:
 losses within 1e-2 and cosine >= 0.99 per gradient tensor against the f32 device step.
 

@@ -116,6 +116,52 @@ def test_variant_without_a_caption_branch():
         net.caption_features(None)
 
 
+# ------------------------------------------------------------------ decoding runs the training forward's own token function
+@pytest.mark.parametrize('model', ['topdown', 'adaatt', 'adaattmo'])
+def test_decoding_step_equals_training_forward_without_a_device(model, monkeypatch):
+    """the entry points restated in torch (TorchOps, as in the host-order tests of tests/test_topdown_cpu.py / test_adaatt_cpu.py, at their
+    SMALL sizes): the training forward in eval mode on S = 4 given tokens, then nets/decode.py's step driven with the same tokens
+    (teacher-forced) on B = 1 row and on B = 2 equal rows.  Every row's logits are the forward's cap.logits row within FWD_TOL.
+    (att2in2's per-token entries have no torch restatement: tests/test_decode_gpu.py test_decode_equals_training_forward holds it.)"""
+    import torch
+    from adaatt_util import TorchOps, ada_opt, cap_state as ada_state
+    from topdown_util import CAP, TorchLinearOp, td_opt, cap_state as td_state, rel_err
+    from test_topdown_cpu import SMALL as TD_SMALL, FWD_TOL
+    from test_adaatt_cpu import SMALL as ADA_SMALL
+    from lang2seg_amd import ops as O
+    from lang2seg_amd._lib import F32
+    from lang2seg_amd.nets import resnet_v1 as RN, decode
+    from lang2seg_amd.nets.params import ParamStore
+    for n in TorchOps.NAMES:
+        monkeypatch.setattr(O, n, getattr(TorchOps, n), raising=False)
+    monkeypatch.setattr(ParamStore, 'refresh_shadow_full', lambda self: None)
+    opt, sd_of = (td_opt(**TD_SMALL), td_state) if model == 'topdown' else (ada_opt(model, **ADA_SMALL), ada_state)
+    S, V, L = 4, opt['vocab_size'], 196
+    net = RN.resnetv1(opt, batch_size=1, num_layers=50)
+    net.device, net.dt = 'cpu', F32
+    net.P = P = ParamStore(opt, 50, 81, 12, 1, 'cpu', F32)
+    P.load_state_dict(sd_of(opt, seed=4))
+    net.att_embed = TorchLinearOp(P, CAP + 'att_embed.0.weight', CAP + 'att_embed.0.bias')
+    g = torch.Generator().manual_seed(11)
+    fc, att = torch.randn(opt['fc_feat_size'], generator=g), torch.randn(L, opt['att_feat_size'], generator=g)
+    words = torch.cat([torch.zeros(1, dtype=torch.int64), torch.randint(1, V + 1, (S,), generator=g)])
+    net.training, net.keep_logprobs, net._cap_loss_weight, net.parity, net._cap_pre = False, False, 1.0, None, None
+    net.t = {'fc_feats': fc.clone()}
+    net._caption_fwd(dict(S=S, cap_in=words[:S].clone(), cap_tgt=words[1:].clone(), cap_mask=torch.ones(S)), att.clone(), torch.zeros(8))
+    want = net.buf('cap.logits', (S, V + 1), torch.float32).clone()
+    assert float(want.abs().max()) > 0
+    cap = net.captioner
+    for B in (1, 2):
+        H = cap.decode_start(*decode._head(net, att.clone()), fc.clone())
+        cur, new = cap.new_states('a', B), cap.new_states('b', B)
+        for i in range(S):
+            logits = decode.step(net, H, cur, new, words[i].repeat(B), B)
+            for r in range(B):
+                e = rel_err(logits[r], want[i])
+                assert e < FWD_TOL, (model, B, i, r, e)
+            cur, new = new, cur
+
+
 def test_predict_tool_takes_the_caption_flags():
     import os
     import sys

@@ -16,6 +16,8 @@ Worst values measured on an MI355X (this file's own prints):
   fixture through the network  greedy log-probabilities 7.0e-07; beam 3 logps 1.2e-06 and p 1.9e-06 absolute (no kept beam carries a -1000)
   decode vs training forward   5.4e-08 (tiny captioners), 4.9e-08 (att2in2 at 512 against the resident launch)
   caption_features             0 against the train branch, both variants"""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -347,6 +349,75 @@ def test_fixture_beam1_kernel_equals_greedy_pick():
     lp = DU.log_softmax(logits.cpu().numpy()[0]).astype(np.float32)
     lp[-1] -= 1000.0
     assert int(toks) == int(np.argmax(lp))
+
+
+# ------------------------------------------------------------------ 3b. the fixture decodes to the parent commit's bits
+# recorded with decode_record on the commit before the captioners moved into nets/captioners.py (twice per captioner, equal results): greedy
+# (seq, logprobs), the beam-3 `beams` as (seq, logps, p, index), and for att2in2 one sampled run with injected draws; floats as hex
+PARENT_DECODE = {
+    'att2in2': {
+        'greedy': ([10, 20, 9, 9, 9, 9], '-0x1.066c76p+1 -0x1.e072d8p+0 -0x1.9c8edep+0 -0x1.a7fc0cp+0 -0x1.a33304p+0 -0x1.a3c15p+0'),
+        'beam3': [
+            ([11, 9, 9, 9, 9, 9], '-0x1.318b24p+1 -0x1.a975eep+0 -0x1.0cf682p+0 -0x1.62e71ap+0 -0x1.6fc8ecp+0 -0x1.7f4a18p+0', '-0x1.2d6f9cp+3', 0),
+            ([11, 9, 9, 9, 5, 16], '-0x1.318b24p+1 -0x1.a975eep+0 -0x1.0cf682p+0 -0x1.62e71ap+0 -0x1.3559e4p+1 -0x1.77325ap+0', '-0x1.4bcap+3', 1),
+            ([11, 9, 9, 9, 9, 10], '-0x1.318b24p+1 -0x1.a975eep+0 -0x1.0cf682p+0 -0x1.62e71ap+0 -0x1.6fc8ecp+0 -0x1.3a86f8p+1', '-0x1.4c2816p+3', 2),
+        ],
+        'sampled': ([6, 18, 5, 17, 10, 10], '-0x1.8ce8c6p+1 -0x1.1d8928p+1 -0x1.2e1be6p+1 -0x1.8ca89p+1 -0x1.54cb7p+0 -0x1.05f424p+1'),
+    },
+    'topdown': {
+        'greedy': ([7], '-0x1.326d7ep-1'),
+        'beam3': [
+            ([7, 0, 0, 0, 0, 0], '-0x1.326d88p-1 -0x1.986e98p-2 0x0p+0 0x0p+0 0x0p+0 0x0p+0', '-0x1.fea4d4p-1', 1),
+            ([0, 0, 0, 0, 0, 0], '-0x1.5533ccp+0 0x0p+0 0x0p+0 0x0p+0 0x0p+0 0x0p+0', '-0x1.5533ccp+0', 0),
+            ([7, 7, 0, 0, 0, 0], '-0x1.326d88p-1 -0x1.2499b6p+0 -0x1.fed64p-1 0x0p+0 0x0p+0 0x0p+0', '-0x1.5e9dccp+1', 3),
+        ],
+    },
+    'adaatt': {
+        'greedy': ([6], '-0x1.12832p+0'),
+        'beam3': [
+            ([0, 0, 0, 0, 0, 0], '-0x1.4f6ef4p+0 0x0p+0 0x0p+0 0x0p+0 0x0p+0 0x0p+0', '-0x1.4f6ef4p+0', 0),
+            ([6, 0, 0, 0, 0, 0], '-0x1.128324p+0 -0x1.09058cp+0 0x0p+0 0x0p+0 0x0p+0 0x0p+0', '-0x1.0dc458p+1', 1),
+            ([18, 0, 0, 0, 0, 0], '-0x1.65aa94p+1 -0x1.5358fp-1 0x0p+0 0x0p+0 0x0p+0 0x0p+0', '-0x1.ba80dp+1', 2),
+        ],
+    },
+    'adaattmo': {
+        'greedy': ([2, 2, 2, 2, 2, 2], '-0x1.43eef6p+0 -0x1.24a19cp+0 -0x1.45854ap+0 -0x1.5f8cbcp+0 -0x1.70ab6ep+0 -0x1.78ca7ap+0'),
+        'beam3': [
+            ([8, 8, 8, 8, 8, 2], '-0x1.b38cp+0 -0x1.cfb1b6p-1 -0x1.08f0dp+0 -0x1.226f66p+0 -0x1.2fd32ep+0 -0x1.1fa054p+0', '-0x1.c58e24p+2', 0),
+            ([8, 8, 8, 8, 8, 8], '-0x1.b38cp+0 -0x1.cfb1b6p-1 -0x1.08f0dp+0 -0x1.226f66p+0 -0x1.2fd32ep+0 -0x1.385b0cp+0', '-0x1.cbbcd4p+2', 1),
+            ([8, 8, 8, 8, 2, 2], '-0x1.b38cp+0 -0x1.cfb1b6p-1 -0x1.08f0dp+0 -0x1.226f66p+0 -0x1.261872p+0 -0x1.7544e4p+0', '-0x1.d88898p+2', 2),
+        ],
+    },
+}
+
+
+def _hx(v):
+    return ' '.join(re.sub(r'\.?0+p', 'p', float(x).hex()) for x in v)       # float32 values: at most six hex digits
+
+
+def decode_record(model):
+    net, fc, att = _fixture_net(model)
+    g = net.caption_decode(att, fc)
+    b = net.caption_decode(att, fc, beam_size=3)
+    rec = {'greedy': (g['seq'], _hx(g['logprobs'])), 'beam3': [(q['seq'], _hx(q['logps']), _hx([q['p']]), q['index']) for q in b['beams']]}
+    if model == 'att2in2':
+        T = net.opt['seq_length']
+        net.parity = {'sample': dev(np.random.RandomState(5).rand(T).astype(np.float32))}
+        try:
+            s = net.caption_decode(att, fc, sample_max=0, temperature=0.8)
+        finally:
+            net.parity = None
+        rec['sampled'] = (s['seq'], _hx(s['logprobs']))
+    return rec
+
+
+@pytest.mark.parametrize('model', MODELS)
+def test_fixture_decodes_the_parents_bits(model):
+    """greedy seq / logprobs, beam-3 beams (seq, logps, p, index) and (att2in2) a sampled run with injected draws: equal, bit for bit, to
+    what the parent commit decoded"""
+    rec = decode_record(model)
+    print('decode record %s: %r' % (model, rec))
+    assert rec == PARENT_DECODE[model]
 
 
 # ------------------------------------------------------------------ 4. decoding equals the training forward

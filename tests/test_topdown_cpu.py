@@ -164,7 +164,7 @@ def test_tools_accept_the_option():
 
 @pytest.mark.parametrize('S,masks', [(1, False), (4, False), (4, True)])
 def test_captioner_host_order_with_torch_kernels(S, masks, monkeypatch):
-    """Network._topdown_pre / _topdown_fwd / _topdown_bwd with every entry point they call restated in torch (topdown_util.TorchOps): the
+    """nets/captioners.py TopDown (pre / fwd / bwd through Network._caption_*) with every entry point it calls restated in torch (topdown_util.TorchOps): the
     host's part - which buffer, column block, transposed block and key goes into which launch, in which order - gives the restatement's
     log-probabilities, loss, parameter gradients and d(att_feats) / d(fc_feats), with injected dropout masks and without"""
     from lang2seg_amd import ops as O

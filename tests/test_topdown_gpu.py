@@ -1,4 +1,4 @@
-"""The top-down attention captioner on the device (csrc/caption_step.hip and nets/resnet_v1.py _topdown_pre / _topdown_fwd / _topdown_bwd)
+"""The top-down attention captioner on the device (csrc/caption_step.hip and nets/captioners.py TopDown)
 against the torch restatement of tests/topdown_util.py, which tests/test_topdown_cpu.py pins to the reference's own model.
 Bounds: the kernel family's (tests/test_kernels_gpu.py rel_err) 1e-5 forward and 1e-4 gradients; 1e-4 on losses in exact-f32 mode; bf16:
 losses within 1e-2 and cosine >= 0.99 per gradient tensor against the f32 device step.
@@ -378,6 +378,9 @@ def default_step_record(variant, keep, opt_over=None, net_over=None):
     opt.update(opt_over or {})
     if opt.get('caption_model') == 'topdown':
         sd = make_sd(opt, seed=3, variant=variant)
+    elif opt.get('caption_model') in ('adaatt', 'adaattmo'):
+        import adaatt_util
+        sd = adaatt_util.make_sd(opt, seed=3, variant=variant)
     elif 'rnn_type' in (opt_over or {}):
         sd = rnn_encoder_util.make_sd(opt, seed=3, variant=variant)
     else:
@@ -420,11 +423,17 @@ RECURRENT_PATHS = {
     'per_token': ({}, dict(cap_persistent=False)),
     'unprojected': ({}, dict(cap_persistent=False, cap_projected=False)),
     'topdown': (dict(caption_model='topdown'), {}),
+    'adaatt': (dict(caption_model='adaatt', adaatt=1), {}),
+    'adaattmo': (dict(caption_model='adaattmo', adaatt=1), {}),
     'gru2_bi': (dict(rnn_type='gru', rnn_num_layers=2, bidirectional=1), {}),
     'rnn1_uni': (dict(rnn_type='rnn', rnn_num_layers=1, bidirectional=0), {}),
     'lstm2_uni': (dict(rnn_type='lstm', rnn_num_layers=2, bidirectional=0), {}),
 }
 PARENT_PATHS = {
+    'adaatt': (545, '23c378d91bc357fa81cd30862d67b3927e55dc74',
+        '0x1.0cd304p-1 0x1.65a62p-6 0x1.2b53a4p+2 0x1.fb1ba2p-13 0x1.55aef6p-1 0x1.079eb8p+2 0x1.40561cp+3'),
+    'adaattmo': (545, '26a271a51d63d0b95e9907ef7ab7239f261b2ee2',
+        '0x1.0cd304p-1 0x1.65a62p-6 0x1.2b53a4p+2 0x1.fb1ba2p-13 0x1.55aef6p-1 0x1.0505f4p+2 0x1.3f09b8p+3'),
     'gru2_bi': (502, '7de52a4f54feac7f0dc17fff5d85c0165ccf1fbe',
         '0x1.64136cp+0 0x1.7c9a62p-5 0x1.3645b6p+2 0x1.5d2148p-12 0x1.6f365p-1 0x1.1b4324p+2 0x1.6db994p+3'),
     'lstm2_uni': (492, '480aefbd69b27ca8ac0ad300543553929af9e345',
@@ -442,7 +451,7 @@ PARENT_PATHS = {
 
 @pytest.mark.parametrize('name', sorted(RECURRENT_PATHS))
 def test_recurrent_paths_compute_the_parents_bits(name):
-    """the per-token att2in2 kernels (projected and unprojected), the top-down captioner and the GRU / tanh-RNN / stacked LSTM encoders:
+    """the per-token att2in2 kernels (projected and unprojected), the top-down and AdaAtt captioners and the GRU / tanh-RNN / stacked LSTM encoders:
     launches, the SHA-1 of the whole gradient buffer and the losses (to 1e-6) of the tiny step are the parent commit's"""
     opt_over, net_over = RECURRENT_PATHS[name]
     n, sha, lv = default_step_record('cycle', True, opt_over, net_over)

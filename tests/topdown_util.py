@@ -220,7 +220,7 @@ sig = torch.sigmoid
 
 
 class TorchOps(object):
-    """lang2seg_amd.ops entries used by Network._topdown_pre / _topdown_fwd / _topdown_bwd, on CPU tensors: the host's order of launches,
+    """lang2seg_amd.ops entries used by nets/captioners.py TopDown (training and the decoding step), on CPU tensors: the host's order of launches,
     buffers, column blocks and keys runs without a device.  The kernels themselves are checked in tests/test_topdown_gpu.py."""
     @staticmethod
     def linear_fwd(x, w, b, y, M, N, K, act=0, accumulate=False, ldx=None, ldy=None, ldw=None):
