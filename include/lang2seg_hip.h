@@ -653,6 +653,34 @@ int l2s_decode_beam_step(const l2s_beam_step_args* a, hipStream_t s);
 /* Device.  dst [H][W] = src [ih][iw] (uint8) resized by PIL NEAREST (csrc/pil_resize.h pil_nearest_src, the rule of the loader's masks). */
 int l2s_mask_resize_nearest(const uint8_t* src, int ih, int iw, uint8_t* dst, int H, int W, hipStream_t s);
 
+/* ---------------------------------------------------------------- the caption branch on rows (nets/caption_rows.py, csrc/caption_rows.hip) ----- */
+/* One row per detection of a sentence.  Every entry takes the `rows` of its buffers, `row0` and `count` (device int32[1], null = all):
+ * row r is live iff row0 + r < *count; a dead row is neither read nor written and no grid depends on *count, so the number of detections
+ * never comes back to the host.  Each row is computed by the arithmetic, in the order, of the single-mask entry named. */
+#define L2S_ROWS_MAX_W 8192       /* blob width of l2s_masks_to_map: its source-column table lives in the LDS */
+/* out f32 {0,1} [rows][Hc * Wc] from masks uint8 [rows][mh][mw]: l2s_mask_resize_nearest to H x W (skipped when (mh, mw) == (H, W)), then
+ * l2s_mask_downsample to Hc x Wc, as one launch; the H x W mask is never stored.  Integer counts: equal to the two launches bit for bit. */
+int l2s_masks_to_map(const uint8_t* masks, int rows, int row0, const int* count, int mh, int mw, int H, int W, int Hc, int Wc, float* out,
+                     hipStream_t s);
+/* y [rows][OH * OW][ldy] (C channels each) = l2s_adaptive_pool_fwd of x [H * W][C] under pm [rows][H * W]; pm null: the unmasked pooling,
+ * summed once and stored to every live row.  dtype of x and y: 0 = f32, 1 = bf16. */
+int l2s_adaptive_pool_rows(const void* x, const float* pm, void* y, int rows, int row0, const int* count, int H, int W, int C, int OH, int OW,
+                           int ldy, int dtype, hipStream_t s);
+/* The att2in2 step in the projected form, per row on the row's own operands (L <= 256, R <= 1024); nothing is kept for backward.
+ * dots [rows][256] = l2s_cap_att_dots_fwd of patt [rows][L][D] and att_h [rows][ld_att_h];
+ * (c, h) [rows][R] = l2s_cap_apply_gates_fwd of P [rows][L][2R], dots, sums [rows][ld_sums] and c_prev [rows][R]. */
+int l2s_cap_att_dots_rows(const float* patt, const float* att_h, int ld_att_h, const float* aw, const float* ab, int rows, int row0,
+                          const int* count, int L, int D, float* dots, hipStream_t s);
+int l2s_cap_apply_gates_rows(const float* P, const float* dots, const float* b_a2c, const float* sums, int ld_sums, const float* c_prev,
+                             float* c, float* h, int rows, int row0, const int* count, int L, int R, hipStream_t s);
+/* One workgroup per row: the log-softmax of logits [rows][ld_logits] over V1, then the argmax (lowest index on equal values) as
+ * l2s_decode_pick takes it with finished int32 [rows] (reset at t == 0: after a 0 every token of the row is 0 with log-probability 0),
+ * or, with `forced` (device int64[1], one token for all rows: teacher forcing, no finished rows), that token and its log-probability.
+ * Writes seq [rows][T] and logprobs [rows][T] at column t, next_token [rows] and, where `sum` f32 [rows] is given, the sum of the row's
+ * log-probabilities so far (set at t == 0, then added to in the order of t). */
+int l2s_decode_pick_rows(const float* logits, int ld_logits, int V1, int rows, int row0, const int* count, int t, int T, const int64_t* forced,
+                         int* finished, int64_t* seq, float* logprobs, int64_t* next_token, float* sum, hipStream_t s);
+
 /* ---------------------------------------------------------------- launch tape / streams ----- */
 /* `to` waits (device side) for everything enqueued so far on `from`; fork or join of the step's branches */
 int l2s_stream_fork(hipStream_t from, hipStream_t to);

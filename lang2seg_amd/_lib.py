@@ -214,6 +214,11 @@ SIGS = {
     'l2s_decode_pick': (i32, [vp, i32, i32, i32, f32, vp, vp, u64, vp, vp, vp, vp, vp]),
     'l2s_decode_beam_step': (i32, [C.POINTER(BeamStepArgs), vp]),
     'l2s_mask_resize_nearest': (i32, [vp, i32, i32, vp, i32, i32, vp]),
+    'l2s_masks_to_map': (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    'l2s_adaptive_pool_rows': (i32, [vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    'l2s_cap_att_dots_rows': (i32, [vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]),
+    'l2s_cap_apply_gates_rows': (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, i32, vp]),
+    'l2s_decode_pick_rows': (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     'l2s_lstm_step_fwd': (i32, [vp, i32, i32, vp]),
     'l2s_lstm_step_bwd': (i32, [vp, i32, i32, vp]),
     'l2s_gru_step_fwd': (i32, [vp, i32, i32, vp]),

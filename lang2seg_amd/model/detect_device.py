@@ -7,7 +7,12 @@ on the device, next to the one-box pick of model/eval_device.py.  Per sentence, 
     l2s_rle_from_masks  the canvases as COCO run lengths in the image's pool (three launches)
 No host synchronisation per sentence; one read-back per image (the records, counts and spans, then the used part of the pool).  Nothing
 is dropped: a sentence with more detections than `cap`, or whose run lengths overflowed the pool, runs again with buffers sized from the
-counts its first run reported (the backbone map of forward_test_image is still there)."""
+counts its first run reported (the backbone map of forward_test_image is still there).
+
+Optionally (detect_image describe= / expr_score=, cycle network) the caption branch on rows runs behind each sentence's detections, on the
+sentence's canvases with the detector's device count (nets/caption_rows.py): what the captioner says about every detection, and the
+teacher-forced log-likelihood of the sentence's own expression under every detection's mask.  Its results stay on the device per sentence
+and come back as one more read-back per image."""
 import numpy as np
 import torch
 
@@ -65,12 +70,69 @@ def detect_sentence(net, s, scale, ih, iw, max_per_image, thresh, cap, rec=None,
     return out
 
 
+class _RowsStage(object):
+    """the caption branch on rows behind a sentence's detections.  tokens: per sentence the expression's ids (its nonzero labels)"""
+
+    def __init__(self, net, tokens, describe, expr_score, ix_to_word=None):
+        from ..nets import caption_rows, decode
+        caption_rows.check_features(net)                          # ValueErrors that name the variant, before any launch
+        decode.check_args(net, 1, 1, 1.0)
+        self.net, self.tokens, self.describe, self.expr_score, self.ix_to_word = net, tokens, bool(describe), bool(expr_score), ix_to_word
+
+    def one(self, i):
+        """the stage of sentence i alone (its re-run)"""
+        return _RowsStage(self.net, [self.tokens[i]], self.describe, self.expr_score, self.ix_to_word)
+
+    def run(self, i, canvases, cap, ih, iw, written):
+        """-> the sentence's results as device copies (the network's row buffers are the next sentence's too)"""
+        net = self.net
+        att, fc = net.caption_features_rows(canvases, cap, (ih, iw), count=written)
+        out = {}
+        if self.describe:
+            r = net.caption_decode_rows(att, fc, rows=cap, count=written)
+            out['seq'], out['lp'] = r['seq'].clone(), r['logprobs'].clone()
+        if self.expr_score:
+            r = net.caption_score_rows(att, fc, self.tokens[i], rows=cap, count=written)
+            out['elp'], out['score'] = r['logprobs'].clone(), r['score'].clone()
+        return out
+
+    KEYS = (('seq', np.int64), ('lp', np.float32), ('elp', np.float32), ('score', np.float32))
+
+    def read_back(self, outs):
+        """one copy for all sentences -> per sentence {key: array}"""
+        parts = [(i, k, dt, o[k]) for i, o in enumerate(outs) for k, dt in self.KEYS if k in o]
+        host = torch.cat([t.reshape(-1).view(torch.uint8) for _, _, _, t in parts]).cpu().numpy()
+        res, off = [dict() for _ in outs], 0
+        for i, k, dt, t in parts:
+            nb = t.numel() * t.element_size()
+            res[i][k] = host[off:off + nb].view(dt).reshape(tuple(t.shape))
+            off += nb
+        return res
+
+    def fields(self, h, k):
+        """the fields of detection k of a sentence from its host arrays h"""
+        p = {}
+        if self.describe:
+            s = h['seq'][k]
+            n = int(np.argmax(s == 0)) if (s == 0).any() else s.size
+            p['caption_tokens'] = [int(v) for v in s[:n]]
+            p['caption_logprobs'] = [float(v) for v in h['lp'][k, :n]]
+            if self.ix_to_word is not None:
+                from .caption_device import decode_sequence
+                p['caption'] = decode_sequence(self.ix_to_word, p['caption_tokens'])
+        if self.expr_score:
+            p['expr_logprob'] = float(h['score'][k])
+            p['expr_logprobs'] = [float(v) for v in h['elp'][k]]
+        return p
+
+
 class _Detector(object):
     """the device side of one image's detections: per sentence `cap` records, the count and the spans in one int32 array (one read-back),
     the image's run-length pool"""
 
-    def __init__(self, net, S, scale, ih, iw, max_per_image, thresh, cap=None, pool_words=None, capture=None):
+    def __init__(self, net, S, scale, ih, iw, max_per_image, thresh, cap=None, pool_words=None, capture=None, stage=None):
         self.net, self.S, self.scale, self.ih, self.iw = net, S, scale, ih, iw
+        self.stage, self.stage_out = stage, [None] * S
         self.max_per_image, self.thresh = int(max_per_image), float(thresh)
         self.cap = cap = default_cap(max_per_image) if cap is None else int(cap)
         self.with_masks = getattr(net, 'variant', None) != 'vgg'
@@ -97,6 +159,8 @@ class _Detector(object):
                           nkeep=None if s['nkeep'] is None else s['nkeep'].clone(), post=s['post'])
         out = detect_sentence(self.net, s, self.scale, self.ih, self.iw, self.max_per_image, self.thresh, self.cap, rec=rec, count=count,
                               spans=spans, pool=self.pool if self.with_masks else None, cursor=self.meta[0:1])
+        if self.stage is not None:                                # on this sentence's canvases, before the next sentence overwrites them
+            self.stage_out[i] = self.stage.run(i, out['canvases'], self.cap, self.ih, self.iw, count[0:1])
         if cap_in is not None:
             if self.with_masks:
                 cap_in['mask_prob'] = out['mask_prob'].clone()
@@ -107,20 +171,22 @@ class _Detector(object):
         not fit its buffers runs again with the sizes its counts ask for)."""
         meta = self.meta.cpu().numpy()
         pool = self.pool[:int(meta[0])].cpu().numpy().view('<u4') if self.with_masks else None
+        rows = None if self.stage is None else self.stage.read_back(self.stage_out)
         out = []
         for i in range(self.S):
             count, rec, spans = self._views(meta, i)
             written, total = int(count[0]), int(count[1])
             fits = total <= self.cap and not (self.with_masks and (spans[:written, 0] < 0).any())
             if fits:
-                out.append(self._dicts(rec[:written], spans[:written], pool, file_name, i, extra))
+                out.append(self._dicts(rec[:written], spans[:written], pool, file_name, i, extra, None if rows is None else rows[i]))
                 continue
             if self.capture is not None:
                 self.capture.append(dict(rerun=i))
             cap = max(total, 1)
             words = int(spans[:written, 1].astype(np.int64).sum()) if total <= self.cap else _pool_budget(cap, self.iw)
             while True:                                            # sizes grow with every round: the counts of `total` masks are a finite sum
-                one = _Detector(self.net, 1, self.scale, self.ih, self.iw, self.max_per_image, self.thresh, cap=cap, pool_words=words)
+                one = _Detector(self.net, 1, self.scale, self.ih, self.iw, self.max_per_image, self.thresh, cap=cap, pool_words=words,
+                                stage=None if self.stage is None else self.stage.one(i))
                 one.run(0, resentence(i))
                 m1 = one.meta.cpu().numpy()
                 c1, r1, s1 = one._views(m1, 0)
@@ -130,11 +196,12 @@ class _Detector(object):
                     words = int(s1[:int(c1[0]), 1].astype(np.int64).sum())
                     continue
                 p1 = one.pool[:int(m1[0])].cpu().numpy().view('<u4') if self.with_masks else None
-                out.append(self._dicts(r1[:int(c1[0])], s1[:int(c1[0])], p1, file_name, i, extra))
+                out.append(self._dicts(r1[:int(c1[0])], s1[:int(c1[0])], p1, file_name, i, extra,
+                                       None if one.stage is None else one.stage.read_back(one.stage_out)[0], one.stage))
                 break
         return out
 
-    def _dicts(self, rec, spans, pool, file_name, i, extra):
+    def _dicts(self, rec, spans, pool, file_name, i, extra, rows=None, stage=None):
         roi, cls, box, score, area = O.det_record_fields(np.ascontiguousarray(rec))
         res = []
         for k in range(rec.shape[0]):
@@ -146,15 +213,30 @@ class _Detector(object):
                 off, n = int(spans[k, 0]), int(spans[k, 1])
                 p['area'] = int(area[k])
                 p['segmentation'] = dict(size=[self.ih, self.iw], counts=O.rle_to_string(pool[off:off + n]))
+            if rows is not None:
+                p.update((stage or self.stage).fields(rows, k))
             res.append(p)
         return res
 
 
-def detect_image(net, data, labels, max_per_image=100, thresh=0.0, _cap=None, _pool_words=None, _capture=None):
+def rows_stage(net, labels, describe, expr_score, ix_to_word=None):
+    """the stage detect_image / eval_split_device run behind every sentence, or None without the options.  ValueError on a network whose
+    caption branch pools no mask (the variant is named)"""
+    if not describe and not expr_score:
+        return None
+    return _RowsStage(net, [[int(w) for w in row if w != 0] for row in np.asarray(labels)], describe, expr_score, ix_to_word)
+
+
+def detect_image(net, data, labels, max_per_image=100, thresh=0.0, _cap=None, _pool_words=None, _capture=None, describe=False, expr_score=False,
+                 ix_to_word=None):
     """data: {'data': float32 (1, H, W, 3) blob, 'im_info': [H, W, scale]} (+ 'file_name'); labels: int [S][T] token ids, zero padded.
     -> one list per sentence of dicts, class ascending and inside a class score descending: file_name, sent_index, roi (the proposal's
     row), category_id, box [x1, y1, x2, y2] (original image), score and (networks with a mask branch) area and segmentation
     {'size': [ih, iw], 'counts': COCO RLE string}.  max_per_image <= 0: no limit; ties at the limit all stay.
+    describe (network 'cycle'): also what the captioner says about each detection's mask, greedy: caption_tokens, caption_logprobs and, with
+    ix_to_word ({str(id): word}), caption.  expr_score: also how well each detection's mask explains the sentence: expr_logprobs, the
+    teacher-forced log-probabilities of the sentence's n tokens and the end token under that mask (n + 1 values), and expr_logprob, their
+    sum.  Both run on the device behind each sentence (nets/caption_rows.py) and cost one more read-back per image.
     (_cap, _pool_words: the buffers' first sizes instead of the defaults; _capture: a list that receives each sentence's head outputs and
     mask probabilities as device copies - checks.)"""
     labels = np.asarray(labels)
@@ -163,6 +245,7 @@ def detect_image(net, data, labels, max_per_image=100, thresh=0.0, _cap=None, _p
     if ((labels != 0).sum(1) == 0).any():
         raise ValueError('labels: every sentence needs at least one token')
     S = int(labels.shape[0])
+    stage = rows_stage(net, labels, describe, expr_score, ix_to_word)
     d = dict(data=data['data'], im_info=data['im_info'], labels=labels.astype(np.int64),
              gt_boxes=np.zeros((S, 5), np.float32), gt_masks=np.zeros((S, 1, 1), np.uint8))
     net.eval()
@@ -171,7 +254,7 @@ def detect_image(net, data, labels, max_per_image=100, thresh=0.0, _cap=None, _p
     scale, ih, iw = ED._geometry(im_info)
     dd = dict(data=img, im_info=im_info, S=1)
     net.forward_test_image(dd)
-    det = _Detector(net, S, scale, ih, iw, max_per_image, thresh, _cap, _pool_words, _capture)
+    det = _Detector(net, S, scale, ih, iw, max_per_image, thresh, _cap, _pool_words, _capture, stage)
 
     def sentence(i):
         dd['labels'] = lab_d[i, :lens[i]]

@@ -155,7 +155,9 @@ def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1, detect=
     det = None
     if detect is not None:
         from .detect_device import _Detector
-        det = detect['detector'] = _Detector(net, n_sent, scale, ih, iw, detect.get('max_per_image', 100), detect.get('thresh', 0.0))
+        from .detect_device import rows_stage
+        stage = rows_stage(net, np.asarray(data['labels'])[:n_sent], detect.get('describe'), detect.get('expr_score'), detect.get('ix_to_word'))
+        det = detect['detector'] = _Detector(net, n_sent, scale, ih, iw, detect.get('max_per_image', 100), detect.get('thresh', 0.0), stage=stage)
         detect['sentence'] = sentence
     for i in range(n_sent):
         s = sentence(i)
@@ -204,7 +206,10 @@ class _Totals(object):
                 details.append((int(roi[j]), int(cls[j]), box[j].copy(), int(hit[j]), int(Is[j]), int(Us[j])))
 
 
-def _run(loader, model, split, opt, rank, world, details, with_masks, progress, predictions=None, pool_words=None, detections=None):
+def _run(loader, model, split, opt, rank, world, details, with_masks, progress, predictions=None, pool_words=None, detections=None,
+         describe=False, expr_score=False):
+    if (describe or expr_score) and detections is None:
+        raise ValueError('describe / expr_score (--describe, --expr_score) add fields to the detections: they need detections (--dump_detections)')
     num_sents = opt.get('num_sents', -1)
     verbose = opt.get('verbose', True)
     if world > 1 and num_sents > 0:
@@ -226,7 +231,8 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
             if num_sents > 0:
                 n = min(n, num_sents - issued)
             rec = O.eval_records(n, device)
-            dopt = None if detections is None else dict(max_per_image=opt.get('max_per_image', 100), thresh=opt.get('det_thresh', 0.0))
+            dopt = None if detections is None else dict(max_per_image=opt.get('max_per_image', 100), thresh=opt.get('det_thresh', 0.0),
+                                                        describe=describe, expr_score=expr_score, ix_to_word=getattr(loader, 'ix_to_word', None))
             if dopt is None:
                 ex = _eval_image(model, data, n, rec, 0, with_masks, -1 if predictions is None else pool_words)
             else:
@@ -264,20 +270,23 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
     return tot
 
 
-def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=None, predictions=None, _pool_words=None, detections=None):
+def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=None, predictions=None, _pool_words=None, detections=None,
+                      describe=False, expr_score=False):
     """model/test.py eval_split on the device.  Returns its 7-tuple (acc, eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U,
     num_sent).  details: a list that receives (pred_roi, pred_class, pred_box, hit, I, U) per sentence of this rank.
     predictions: a list that receives one dict per sentence of this rank: file_name, sent_index (position in the image's test batch),
     category_id, box [x1, y1, x2, y2] (original image), score, hit, I, U and segmentation {'size': [ih, iw], 'counts': COCO RLE string}.
     detections: a list that receives every detection of every sentence of this rank (model/detect_device.py detect_image's dicts, flat;
     opt['max_per_image'] (100) and opt['det_thresh'] (0.0) are its limits).  Metrics and predictions do not depend on it.
+    describe / expr_score: detect_image's options for those detections (the captioner on every detection; the expression's log-likelihood
+    under every detection's mask); they need `detections` and the cycle network.
     (_pool_words: the run-length pool of an image in words instead of its default budget; checks of the host fallback.)"""
     def progress(data, t):
         b = data['bounds']
         print('evaluating [%s] ... image[%d/%d]\'s sents, det acc=%.2f%%, seg acc=%.2f%%, seg IoU=%.2f%%' % (
             split, b['it_pos_now'], b['it_max'], t.acc * 100.0 / max(t.loss_evals, 1), t.seg_correct[0] * 100.0 / max(t.seg_total, 1),
             t.cum_I * 100.0 / max(t.cum_U, 1)))
-    t = _run(loader, model, split, opt, rank, world, details, True, progress, predictions, _pool_words, detections)
+    t = _run(loader, model, split, opt, rank, world, details, True, progress, predictions, _pool_words, detections, describe, expr_score)
     return t.acc / t.loss_evals, EVAL_SEG_IOU_LIST, t.seg_correct, t.seg_total, t.cum_I, t.cum_U, t.num_sent
 
 

@@ -1,0 +1,200 @@
+"""The caption branch on rows: one row per detection of a sentence (model/detect_device.py hands over a sentence's canvases and the
+detector's device count).  Network.caption_features_rows pools layer4 under every mask in one launch per pooling; caption_decode_rows
+decodes every row greedily; caption_score_rows scores ONE expression, teacher-forced, under every row's mask: the log-likelihood the
+cycle loss minimises for the ground-truth mask (AttModel.forward + a gather, LanguageModelCriterion's mask all ones).
+
+Two routes:
+  batched   att2in2 in the projected form (L = 196 <= 256, rnn_size <= 1024): the head as GEMMs on rows * 196 rows, then per token
+            [embedding, i2h] (greedy; scoring does both once for all n + 1 inputs) -> h2h and h2att as row-batch Linears -> the row-strided
+            attention dots and softmax + gates (csrc/caption_rows.hip) -> logit Linear -> l2s_decode_pick_rows.  8 launches a token (6 when
+            scoring) whatever `rows` and `count` are; `count` stays on the device.
+  loop      every other captioner, `net.rows_batched = False`, or shapes outside the limits: the single-mask launches of nets/decode.py row
+            by row (head, decode_start, T x step), the decision by l2s_decode_pick_rows on one row.  Reads `count` back once per call.
+            Slow (about rows * 3 T dependent launches) but correct for every captioner, and the cross-check of the batched route.
+
+Rows are processed in chunks of at most CHUNK = 64, so the head's products (a, patt, P: 196 * 64 rows of 4 rnn_size + att_hid_size floats)
+stay near 0.1 GB at the production widths beside the chunk's 0.1 GB of features.  Every buffer is `rows.*` (the loop also uses decoding's
+`dec.*`): a call between a training forward and its backward leaves what that backward reads alone.  The results are the network's buffers:
+valid until the next call."""
+import numpy as np
+import torch
+
+from .. import ops as O
+from . import decode
+
+f32, i32, i64 = torch.float32, torch.int32, torch.int64
+L = 196
+CHUNK = 64
+
+
+def check_features(net):
+    """ValueErrors that name the variant: only the cycle network pools under a mask"""
+    variant = getattr(net, 'variant', '?')
+    if variant == 'vgg' or not getattr(net, 'layers', {}).get(4):
+        raise ValueError('--variant %s: the VGG network has no caption branch, nothing to pool per detection (cycle has one)' % variant)
+    if getattr(net, 'var', None) is None or net.var.get('cap') is None or not hasattr(net, 'att_embed'):
+        raise ValueError('--variant %s has no caption branch: nothing to pool per detection (cycle has one)' % variant)
+    if net.var['cap'] != 'mask':
+        raise ValueError('--variant %s pools no mask (its caption features are the map before and after the gating): every detection would get '
+                         'the same features; captions per detection need --variant cycle' % variant)
+
+
+def caption_features_rows(net, masks, rows, shape, count=None):
+    """masks uint8 [rows][mh][mw], shape = (mh, mw): any size, resized to the blob's by PIL NEAREST as the loader's masks are.
+    -> (att_feats [rows][196][att_feat_size], fc_feats [rows][fc_feat_size] or None) of the sentence whose TEST forward ran last: one
+    layer4 pass on the map, the masks at the map's size in one launch, one pooling launch per half.  count: device int32 [1], the live rows."""
+    check_features(net)
+    p = getattr(net, '_test_sentence', None)
+    if p is None:
+        raise RuntimeError('caption_features_rows follows forward_test_sentence: no TEST forward has run')
+    rows, (mh, mw) = int(rows), (int(shape[0]), int(shape[1]))
+    if rows < 1 or masks.dtype != torch.uint8 or masks.numel() != rows * mh * mw:
+        raise ValueError('caption_features_rows: masks is uint8 [rows = %d][%d][%d]' % (rows, mh, mw))
+    net_conv, (Hc, Wc), (H, W) = p['net_conv'], p['net_conv_hw'], p['blob_hw']
+    AF, FC = net.opt['att_feat_size'], net.opt.get('fc_feat_size')
+    feats = net._l4_on_map(net_conv, Hc, Wc, 'l4m')
+    gm = net.buf('rows.gm', (rows, Hc * Wc), f32)
+    O.masks_to_map(masks, rows, mh, mw, H, W, Hc, Wc, gm, count)
+    att, fc = net.buf('rows.att', (rows, L, AF)), None
+    for j, m in enumerate((None, gm)):
+        O.adaptive_pool_rows(feats, m, att.view(-1)[2048 * j:], rows, Hc, Wc, 2048, 14, 14, AF, count)
+    if net.captioner.reads_fc:
+        if FC != 2 * 2048:
+            raise ValueError('fc_feat_size %r: fc_feats is the pair of 2048-channel means of layer4 on the map (4096)' % (FC,))
+        fc = net.buf('rows.fc', (rows, FC))
+        for j, m in enumerate((None, gm)):
+            O.adaptive_pool_rows(feats, m, fc.view(-1)[2048 * j:], rows, Hc, Wc, 2048, 1, 1, FC, count)
+    return att, fc
+
+
+def batched(net):
+    """the batched route serves this network: att2in2, projected, inside the row kernels' limits"""
+    cap = net.captioner
+    return bool(getattr(net, 'rows_batched', True)) and net.cap_model == 'att2in2' and bool(cap.proj()) and net.opt['rnn_size'] <= 1024
+
+
+def _start(net, what, att_feats, fc_feats, rows, count):
+    decode.check_args(net, 1, 1, 1.0)
+    if net.training:
+        raise RuntimeError('%s runs in eval mode (net.eval()): the dropouts are off' % what)
+    rows = int(rows)
+    AF, FC = net.opt['att_feat_size'], net.opt.get('fc_feat_size')
+    if rows < 1 or att_feats.numel() != rows * L * AF:
+        raise ValueError('%s: att_feats has %d values, expected rows x 196 x att_feat_size = %d' % (what, att_feats.numel(), max(rows, 0) * L * AF))
+    want = O.TORCH_DT[net.dt]
+    if att_feats.dtype != want:
+        raise ValueError('%s: att_feats is %s, the network computes in %s' % (what, att_feats.dtype, want))
+    if net.captioner.reads_fc and (fc_feats is None or fc_feats.numel() != rows * FC):
+        raise ValueError('%s: --caption_model %s reads fc_feats [rows][fc_feat_size = %d]' % (what, net.cap_model, FC))
+    if count is not None and (count.dtype != i32 or count.numel() < 1):
+        raise ValueError('%s: count is a device int32 [1]' % what)
+    net.join_update()
+    net.join_transposes()
+    att = att_feats.contiguous().view(rows, L * AF)
+    fc = fc_feats.contiguous().view(rows, FC) if net.captioner.reads_fc else None
+    return rows, att, fc
+
+
+def _outputs(net, rows, T):
+    """seq int64 | log-probabilities f32 | their sums f32 in one zeroed buffer (a dead row reads as an empty sentence), and the flags"""
+    out = net.buf('rows.out', (rows * (12 * T + 4),), torch.uint8, zero=True)
+    seq = out[:8 * rows * T].view(i64).view(rows, T)
+    lps = out[8 * rows * T:12 * rows * T].view(f32).view(rows, T)
+    score = out[12 * rows * T:].view(f32)
+    return seq, lps, score, net.buf('rows.finished', (rows,), i32)
+
+
+def _run_batched(net, att, rows, count, T, seq, lps, score, fin, inputs=None, targets=None):
+    """inputs / targets: device int64 [T] for teacher forcing (None: greedy)"""
+    cap = net.captioner
+    R, IE, AH = cap.dims()
+    AF, V1 = net.opt['att_feat_size'], net.opt['vocab_size'] + 1
+    pv = cap.pv
+    nb = min(rows, CHUNK)
+    b = lambda n, shp, zero=False: net.buf('rows.' + n, shp, f32, zero)
+    a, patt, Pm = b('a', (nb * L, R)), b('patt', (nb * L, AH)), b('P', (nb * L, 2 * R))
+    sums, att_h, dots, logits = b('sums', (nb, 5 * R)), b('att_h', (nb, AH)), b('dots', (nb, 256)), b('logits', (nb, V1))
+    xt = b('xt', (nb, IE))
+    tokens = net.buf('rows.tokens', (nb,), i64)
+    forced = inputs is not None
+    if forced:
+        # the token-only work, once for all rows: the embedding and i2h of the T inputs; h2h's bias joins each row
+        xs, bias = b('xt_all', (T, IE)), b('bias_all', (T, 5 * R))
+        O.embed_fwd(pv('embed.0.weight'), inputs, None, xs, T, IE, True)
+        cap.token_inputs(xs, bias, T)
+        for t in range(T):
+            O.add_f32(bias[t], pv('core.h2h.bias'), bias[t])
+    for c0 in range(0, rows, CHUNK):
+        n = min(CHUNK, rows - c0)
+        # the head of n rows: att_embed (Linear + ReLU), ctx2att and P = att . W_a2c^T as GEMMs on n * 196 rows
+        net.att_embed.fwd(att[c0:c0 + n], n * L, 1, 1, a, relu=True, out_f32=True)
+        O.linear_fwd(a, pv('ctx2att.weight'), pv('ctx2att.bias'), patt, n * L, AH, R)
+        O.linear_fwd(a, pv('core.a2c.weight'), None, Pm, n * L, 2 * R, R)
+        st = [(b('h.' + k, (nb, R), True), b('c.' + k, (nb, R), True)) for k in 'ab']
+        O.memset_zero(tokens)                                   # <bos>; a dead row's slot stays a valid index for the embedding
+        for t in range(T):
+            (h0, cp), (h1, c1) = st[t & 1], st[1 - (t & 1)]
+            if forced:
+                O.linear_fwd(h0, pv('core.h2h.weight'), bias[t], sums, n, 5 * R, R)
+            else:
+                O.embed_fwd(pv('embed.0.weight'), tokens, None, xt, n, IE, True)
+                cap.token_inputs(xt, sums, n)
+                O.linear_fwd(h0, pv('core.h2h.weight'), pv('core.h2h.bias'), sums, n, 5 * R, R, accumulate=True)
+            O.linear_fwd(h0, pv('core.attention.h2att.weight'), pv('core.attention.h2att.bias'), att_h, n, AH, R)
+            O.cap_att_dots_rows(patt, att_h, pv('core.attention.alpha_net.weight'), pv('core.attention.alpha_net.bias'), n, L, AH, dots, count, c0)
+            O.cap_apply_gates_rows(Pm, dots, pv('core.a2c.bias'), sums, cp, c1, h1, n, L, R, count, c0)
+            O.linear_fwd(h1, pv('logit.weight'), pv('logit.bias'), logits, n, V1, R)
+            O.decode_pick_rows(logits, V1, n, t, T, fin[c0:], seq[c0:], lps[c0:], tokens, targets[t:t + 1] if forced else None, count, c0,
+                               score=score[c0:])
+
+
+def _run_loop(net, att, fc, rows, count, T, seq, lps, score, fin, targets=None):
+    """the single-mask launches row by row; the one read-back of `count`"""
+    cap = net.captioner
+    V1 = net.opt['vocab_size'] + 1
+    n = rows if count is None else max(0, min(rows, int(count[0:1].cpu()[0])))
+    tokens = net.buf('rows.token', (1,), i64)
+    for r in range(n):
+        ad, patt = decode._head(net, att[r])
+        H = cap.decode_start(ad, patt, decode._fc_checked(net, fc[r]) if cap.reads_fc else None)
+        O.memset_zero(tokens)
+        cur, new = cap.new_states('a', 1), cap.new_states('b', 1)
+        for t in range(T):
+            logits = decode.step(net, H, cur, new, tokens, 1)
+            O.decode_pick_rows(logits, V1, 1, t, T, fin[r:], seq[r:], lps[r:], tokens, None if targets is None else targets[t:t + 1],
+                               score=score[r:])
+            cur, new = new, cur
+
+
+def caption_decode_rows(net, att_feats, fc_feats=None, rows=None, count=None, sample_max=1, beam_size=1):
+    """greedy decoding of `rows` masks at once -> {'seq': int64 [rows][seq_length], 'logprobs': f32 [rows][seq_length]} on the device, zero
+    from a row's first 0 on and in the rows at or beyond count[0]; no read-back on the batched route"""
+    if not sample_max or beam_size != 1:
+        raise ValueError('--sample_max %r --beam_size %r: decoding on rows is greedy (--sample_max 1 --beam_size 1); sampled and beam decoding '
+                         'take one mask at a time (caption_decode)' % (sample_max, beam_size))
+    rows, att, fc = _start(net, 'caption_decode_rows', att_feats, fc_feats, att_feats.shape[0] if rows is None else rows, count)
+    T = int(net.opt['seq_length'])
+    seq, lps, score, fin = _outputs(net, rows, T)
+    if batched(net):
+        _run_batched(net, att, rows, count, T, seq, lps, score, fin)
+    else:
+        _run_loop(net, att, fc, rows, count, T, seq, lps, score, fin)
+    return {'seq': seq, 'logprobs': lps}
+
+
+def caption_score_rows(net, att_feats, fc_feats, tokens, rows=None, count=None):
+    """one expression (tokens: ints 1 .. vocab_size, any length n >= 1) against `rows` masks, teacher-forced with the inputs
+    [0, w_1 .. w_n] and the targets [w_1 .. w_n, 0] -> {'logprobs': f32 [rows][n + 1], 'score': f32 [rows] their sum} on the device"""
+    toks = [int(v) for v in np.asarray(tokens).reshape(-1)]
+    V = int(net.opt['vocab_size']) if getattr(net, 'opt', None) else 0
+    if not toks or min(toks) < 1 or max(toks) > V:
+        raise ValueError('caption_score_rows: tokens are ints 1 .. vocab_size = %d, at least one; got %r' % (V, toks[:8]))
+    rows, att, fc = _start(net, 'caption_score_rows', att_feats, fc_feats, att_feats.shape[0] if rows is None else rows, count)
+    T = len(toks) + 1
+    io = torch.tensor([[0] + toks, toks + [0]], dtype=i64).to(net.device)
+    seq, lps, score, fin = _outputs(net, rows, T)
+    if batched(net):
+        _run_batched(net, att, rows, count, T, seq, lps, score, fin, io[0], io[1])
+    else:
+        _run_loop(net, att, fc, rows, count, T, seq, lps, score, fin, io[1])
+    return {'logprobs': lps, 'score': score}

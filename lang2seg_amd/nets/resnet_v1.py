@@ -18,6 +18,7 @@ from .captioners import CAPTIONERS
 from .variants import solver_cfg
 from . import anchors as ANC
 from . import decode
+from . import caption_rows
 
 f32 = torch.float32
 
@@ -1121,3 +1122,18 @@ class resnetv1(Network):
         """greedy (sample_max = 1), sampled (sample_max = 0, temperature) or beam-search (beam_size > 1) decoding of the selected captioner on
         the device, eval mode: {'seq', 'logprobs'} (+ 'beams' for beam search).  nets/decode.py"""
         return decode.caption_decode(self, att_feats, fc_feats, sample_max, beam_size, temperature)
+
+    # ------------------------------------------------------------------ the same on rows: one row per detection (nets/caption_rows.py)
+    def caption_features_rows(self, masks, rows, shape, count=None):
+        """caption_features under `rows` uint8 masks [rows][shape[0]][shape[1]] at once (network 'cycle'): (att_feats [rows][196][att_feat_size],
+        fc_feats [rows][fc_feat_size] or None); count: device int32 [1], the rows in use"""
+        return caption_rows.caption_features_rows(self, masks, rows, shape, count)
+
+    def caption_decode_rows(self, att_feats, fc_feats=None, rows=None, count=None, sample_max=1, beam_size=1):
+        """greedy decoding of `rows` masks at once -> device tensors {'seq' int64 [rows][seq_length], 'logprobs' f32 [rows][seq_length]}"""
+        return caption_rows.caption_decode_rows(self, att_feats, fc_feats, rows, count, sample_max, beam_size)
+
+    def caption_score_rows(self, att_feats, fc_feats, tokens, rows=None, count=None):
+        """the teacher-forced log-likelihood of one expression (ints 1 .. vocab_size, length n) under `rows` masks -> device tensors
+        {'logprobs' f32 [rows][n + 1], 'score' f32 [rows]}"""
+        return caption_rows.caption_score_rows(self, att_feats, fc_feats, tokens, rows, count)

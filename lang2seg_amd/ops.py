@@ -811,6 +811,64 @@ def mask_resize_nearest(src, ih, iw, dst, H, W):
     call('l2s_mask_resize_nearest', ptr(src), int(ih), int(iw), ptr(dst), int(H), int(W), stream())
 
 
+# ------------------------------------------------------------------ the caption branch on rows (csrc/caption_rows.hip)
+# rows: the rows of the buffers; row r is live iff row0 + r < count[0] (count: device int32 [1], None = all)
+def _rows_count(name, rows, row0, count):
+    if rows < 1 or row0 < 0:
+        raise ValueError('%s: rows = %r, row0 = %r' % (name, rows, row0))
+    if count is not None and (count.dtype != torch.int32 or count.numel() < 1):
+        raise ValueError('%s: count is a device int32 [1]' % name)
+
+
+def masks_to_map(masks, rows, mh, mw, H, W, Hc, Wc, out, count=None, row0=0):
+    """out f32 {0,1} [rows][Hc * Wc] = mask_resize_nearest to H x W (skipped when the masks have that size) + mask_downsample of masks
+    uint8 [rows][mh][mw], one launch"""
+    _rows_count('masks_to_map', rows, row0, count)
+    if masks.dtype != torch.uint8 or masks.numel() < rows * mh * mw or out.dtype != torch.float32 or out.numel() < rows * Hc * Wc:
+        raise ValueError('masks_to_map: a buffer is smaller than its shape, or not uint8 -> float32')
+    call('l2s_masks_to_map', ptr(masks), int(rows), int(row0), ptr(count), int(mh), int(mw), int(H), int(W), int(Hc), int(Wc), ptr(out), stream())
+
+
+def adaptive_pool_rows(x, pixmasks, y, rows, H, W, Cc, OH, OW, ldy, count=None, row0=0):
+    """y [rows][OH * OW][ldy] = adaptive_pool_fwd of x [H * W][Cc] under pixmasks f32 [rows][H * W] (None: unmasked, every row alike)"""
+    _rows_count('adaptive_pool_rows', rows, row0, count)
+    if x.numel() < H * W * Cc or x.dtype != y.dtype or ldy < Cc or (pixmasks is not None and (pixmasks.dtype != torch.float32 or pixmasks.numel() < rows * H * W)):
+        raise ValueError('adaptive_pool_rows: a buffer is smaller than its shape, or the dtypes differ')
+    call('l2s_adaptive_pool_rows', ptr(x), ptr(pixmasks), ptr(y), int(rows), int(row0), ptr(count), H, W, Cc, OH, OW, ldy, dt_of(x), stream())
+
+
+def cap_att_dots_rows(patt, att_h, aw, ab, rows, L, D, dots, count=None, row0=0, ld_att_h=None):
+    """dots f32 [rows][256] = cap_att_dots_fwd per row of patt [rows][L][D] and att_h [rows][D]"""
+    _rows_count('cap_att_dots_rows', rows, row0, count)
+    if patt.numel() < rows * L * D or dots.numel() < rows * 256 or L > 256:
+        raise ValueError('cap_att_dots_rows: a buffer is smaller than rows = %d asks, or L = %d > 256' % (rows, L))
+    call('l2s_cap_att_dots_rows', ptr(patt), ptr(att_h), D if ld_att_h is None else ld_att_h, ptr(aw), ptr(ab), int(rows), int(row0), ptr(count), L, D,
+         ptr(dots), stream())
+
+
+def cap_apply_gates_rows(P, dots, b_a2c, sums, c_prev, c, h, rows, L, R, count=None, row0=0, ld_sums=None):
+    """(c, h) [rows][R] = cap_apply_gates_fwd per row of P [rows][L][2R], dots [rows][256], sums [rows][5R], c_prev [rows][R]"""
+    _rows_count('cap_apply_gates_rows', rows, row0, count)
+    if P.numel() < rows * L * 2 * R or dots.numel() < rows * 256 or min(c_prev.numel(), c.numel(), h.numel()) < rows * R or L > 256 or R > 1024:
+        raise ValueError('cap_apply_gates_rows: a buffer is smaller than rows = %d asks, or L = %d > 256, or R = %d > 1024' % (rows, L, R))
+    call('l2s_cap_apply_gates_rows', ptr(P), ptr(dots), ptr(b_a2c), ptr(sums), 5 * R if ld_sums is None else ld_sums, ptr(c_prev), ptr(c), ptr(h),
+         int(rows), int(row0), ptr(count), L, R, stream())
+
+
+def decode_pick_rows(logits, V1, rows, t, T, finished, seq, logprobs, next_token, forced=None, count=None, row0=0, ld_logits=None, score=None):
+    """per row of logits f32 [rows][V1]: the greedy decision of decode_pick, or with forced (device int64 [1]) that token and its
+    log-probability; finished int32 [rows], seq int64 [rows][T], logprobs f32 [rows][T] (column t), next_token int64 [rows], score f32 [rows]
+    (optional): the sum of the row's log-probabilities up to t"""
+    _rows_count('decode_pick_rows', rows, row0, count)
+    ld = V1 if ld_logits is None else ld_logits
+    if logits.numel() < (rows - 1) * ld + V1 or not 0 <= t < T or min(seq.numel(), logprobs.numel()) < rows * T or \
+            min(finished.numel(), next_token.numel()) < rows or seq.dtype != torch.int64 or next_token.dtype != torch.int64 or \
+            (forced is not None and forced.dtype != torch.int64) or (score is not None and score.numel() < rows):
+        raise ValueError('decode_pick_rows: a buffer is smaller than rows = %d / V1 = %d / t = %d of T = %d ask, or has the wrong dtype' % (rows, V1, t, T))
+    call('l2s_decode_pick_rows', ptr(logits), int(ld), int(V1), int(rows), int(row0), ptr(count), int(t), int(T), ptr(forced), ptr(finished), ptr(seq),
+         ptr(logprobs), ptr(next_token), ptr(score), stream())
+
+
 def rcnn_predict(heads, ldh, R, ncls, stds4, means4, cls_prob, bbox_pred):
     call('l2s_rcnn_predict', ptr(heads), ldh, R, ncls, ptr(stds4), ptr(means4), ptr(cls_prob), ptr(bbox_pred), stream())
 

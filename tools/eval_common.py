@@ -32,6 +32,10 @@ def parse_args(argv=None):
                    'cfg.TEST.NMS, --max_per_image, --det_thresh; box, score, area, COCO RLE mask) as one JSON list to this path (rank suffix as above)')
     p.add_argument('--max_per_image', type=int, default=100, help='--dump_detections: detections kept per sentence over all classes (<= 0: all)')
     p.add_argument('--det_thresh', type=float, default=0.0, help='--dump_detections: a detection needs a score above this')
+    p.add_argument('--describe', type=int, default=0, help='--dump_detections on the cycle network: also what the captioner says about every '
+                   'detection (caption_tokens, caption_logprobs, caption; greedy)')
+    p.add_argument('--expr_score', type=int, default=0, help='--dump_detections on the cycle network: also the log-likelihood of the sentence '
+                   'under every detection\'s mask (expr_logprob, expr_logprobs)')
     # the expression encoder the snapshot was trained with (tools/opt.py; a snapshot of another encoder is an error that names the flag)
     # (default None: tools/opt.py's own defaults apply)
     p.add_argument('--rnn_type', default=None, help='lstm, gru or rnn'); p.add_argument('--rnn_num_layers', type=int, default=None)
@@ -64,6 +68,11 @@ def main(args, variant):
         raise ValueError('--dump_predictions needs --device_eval 1 (the host loop keeps no predictions)')
     if args.get('dump_detections') and not args['device_eval']:
         raise ValueError('--dump_detections needs --device_eval 1 (the host loop keeps one box per sentence)')
+    for k in ('describe', 'expr_score'):
+        if args.get(k) and not args.get('dump_detections'):
+            raise ValueError('--%s 1 needs --dump_detections PATH: it adds fields to every detection (--%s, --dump_detections)' % (k, k))
+    if (args.get('describe') or args.get('expr_score')) and variant == 'vgg':
+        raise ValueError('--describe / --expr_score: --variant vgg has no caption branch (the cycle network has one)')
     preds = [] if args.get('dump_predictions') else None
     dets = [] if args.get('dump_detections') else None
     torch.cuda.set_device(local % max(torch.cuda.device_count(), 1))
@@ -126,7 +135,8 @@ def main(args, variant):
                 det_thresh=args.get('det_thresh', 0.0))
     if args['device_eval']:
         from lang2seg_amd.model.eval_device import eval_split_device
-        res = eval_split_device(loader, net, None, split, eopt, rank=rank, world=world, predictions=preds, detections=dets)
+        res = eval_split_device(loader, net, None, split, eopt, rank=rank, world=world, predictions=preds, detections=dets,
+                                describe=bool(args.get('describe')), expr_score=bool(args.get('expr_score')))
         dump_predictions(args, preds, rank, world)
         dump_predictions(args, dets, rank, world, 'dump_detections', 'detections')
     else:

@@ -6,7 +6,10 @@ Prints one JSON list: per sentence the class, the box, the score, the mask's are
 each mask as DIR/<image>_<sent_index>.png, decoded on the device from the run lengths (l2s_rle_to_mask): the round trip.
     --all_detections 1 [--max_per_image N] [--det_thresh T]: every instance the network finds for each sentence instead of its first
 pick (model/detect_device.py: class-wise NMS with cfg.TEST.NMS, the best N over all classes); prints one list per sentence, --png writes
-DIR/<image>_<sent_index>_<k>.png.
+DIR/<image>_<sent_index>_<k>.png.  With it, --describe 1 adds what the captioner says about EVERY detection (caption_tokens,
+caption_logprobs, caption; greedy) and --expr_score 1 how well every detection's mask explains the sentence (expr_logprob: the
+teacher-forced log-likelihood of the sentence under that mask, expr_logprobs: per token and the end token); both need --variant cycle
+(nets/caption_rows.py) and either without --all_detections 1 is an error.
     --caption 1 [--beam_size B] [--sample_max 0|1] [--temperature t]: also what the captioner says about each predicted mask
 (model/caption_device.py: the caption branch's features under the mask, decoded on the device: greedy by default, sampled with
 --sample_max 0, beam search with --beam_size > 1); adds caption_tokens, caption_logprobs and caption to every sentence's dict.  The
@@ -37,6 +40,7 @@ def parse_args(argv=None):
     p.add_argument('--allow_init_weights', type=int, default=0)
     p.add_argument('--all_detections', type=int, default=0); p.add_argument('--max_per_image', type=int, default=100)
     p.add_argument('--det_thresh', type=float, default=0.0)
+    p.add_argument('--describe', type=int, default=0); p.add_argument('--expr_score', type=int, default=0)
     # the expression encoder the snapshot was trained with (tools/opt.py; a snapshot of another encoder is an error that names the flag)
     # (default None: tools/opt.py's own defaults apply)
     p.add_argument('--rnn_type', default=None, help='lstm, gru or rnn'); p.add_argument('--rnn_num_layers', type=int, default=None)
@@ -67,6 +71,9 @@ def write_png(pred, path):
 def main(args):
     if args.get('all_detections') and args.get('caption'):
         raise ValueError('--caption 1 with --all_detections 1: a caption describes the one mask picked for a sentence, not each detection; give one of the two')
+    for k in ('describe', 'expr_score'):
+        if args.get(k) and not args.get('all_detections'):
+            raise ValueError('--%s 1 without --all_detections 1: it adds fields to every detection; give --all_detections 1 with --%s 1' % (k, k))
     from lang2seg_amd import ops as O
     from lang2seg_amd.model.config import cfg, cfg_from_file
     from lang2seg_amd.model.predict_device import predict_image
@@ -112,7 +119,11 @@ def main(args):
         raise FileNotFoundError('no snapshot at %s (--allow_init_weights 1 predicts with the initialisers)' % ckpt)
     if args.get('all_detections'):
         from lang2seg_amd.model.detect_device import detect_image
-        dets = detect_image(net, data, labels, max_per_image=args['max_per_image'], thresh=args['det_thresh'])
+        words = None
+        if args.get('describe'):
+            words = {str(i): 'w%d' % i for i in range(1, loader.vocab_size + 1)} if args['synthetic'] else loader.ix_to_word
+        dets = detect_image(net, data, labels, max_per_image=args['max_per_image'], thresh=args['det_thresh'], describe=bool(args.get('describe')),
+                            expr_score=bool(args.get('expr_score')), ix_to_word=words)
         if args['png']:
             os.makedirs(args['png'], exist_ok=True)
             for lst in dets:
