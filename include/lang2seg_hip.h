@@ -680,6 +680,22 @@ int l2s_cap_apply_gates_rows(const float* P, const float* dots, const float* b_a
  * log-probabilities so far (set at t == 0, then added to in the order of t). */
 int l2s_decode_pick_rows(const float* logits, int ld_logits, int V1, int rows, int row0, const int* count, int t, int T, const int64_t* forced,
                          int* finished, int64_t* seq, float* logprobs, int64_t* next_token, float* sum, hipStream_t s);
+/* The top-down step on rows.  l2s_lstm_cell_rows: one nn.LSTMCell step (gate order i, f, g, o; l2s_topdown_cell_fwd's arithmetic) for every
+ * live row in one launch:
+ *   gates[r][4R] = pre[r * ld_pre] + pre2[r * ld_pre2] + add0 + add1 + sum over up to two segments w_k[4R][:n_k] . x_k[r * ldx_k][:n_k]
+ * pre / pre2: NULL or [4R] per row with a row stride (0: one row for all rows); add0 / add1: NULL or [4R]; w_k: a column block (leading
+ * dimension ld_k) of a wider matrix; a segment with n = 0 is skipped.  c_prev, c and h have their own row strides (h may be the second
+ * half of a [rows][2R] array).  c and h must not alias c_prev or a segment's x.  The products run on the exact-fp32 MFMA: a workgroup owns
+ * the four gate rows of 4 hidden units for a tile of 16 (rows <= 16) or 32 rows, so a weight element is fetched once per tile of rows.
+ * Segments whose length, strides or addresses are not multiples of 4 floats take scalar loads.  R >= 1, any rows >= 1. */
+typedef struct { const float* x; int ldx; const float* w; int ld; int n; } l2s_rows_seg;
+typedef struct { const float* pre; int ld_pre; const float* pre2; int ld_pre2; const float* add0; const float* add1; l2s_rows_seg seg[2];
+                 const float* c_prev; int ld_c_prev; float* c; int ld_c; float* h; int ld_h; } l2s_lstm_rows;
+int l2s_lstm_cell_rows(const l2s_lstm_rows* a, int R, int rows, int row0, const int* count, hipStream_t s);
+/* att_res[r * ld_res][:R] = l2s_cap_att_apply_fwd of att [rows][L][R] and dots [rows][256] per live row (no `weight` output), in that
+ * kernel's summation order: the same bits as the single-row launch.  L <= 256, ld_res >= R. */
+int l2s_cap_att_apply_rows(const float* att, const float* dots, float* att_res, int ld_res, int rows, int row0, const int* count, int L, int R,
+                           hipStream_t s);
 
 /* ---------------------------------------------------------------- launch tape / streams ----- */
 /* `to` waits (device side) for everything enqueued so far on `from`; fork or join of the step's branches */

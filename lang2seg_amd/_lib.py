@@ -80,6 +80,15 @@ class TopdownBwd(C.Structure):
                 ('dc_prev', vp)]
 
 
+class RowsSeg(C.Structure):
+    _fields_ = [('x', vp), ('ldx', i32), ('w', vp), ('ld', i32), ('n', i32)]
+
+
+class LstmRows(C.Structure):
+    _fields_ = [('pre', vp), ('ld_pre', i32), ('pre2', vp), ('ld_pre2', i32), ('add0', vp), ('add1', vp), ('seg', RowsSeg * 2),
+                ('c_prev', vp), ('ld_c_prev', i32), ('c', vp), ('ld_c', i32), ('h', vp), ('ld_h', i32)]
+
+
 class AdaattFwd(C.Structure):
     _fields_ = [(n, vp) for n in ('pre', 'fcrow', 'w_hh', 'b_hh', 'w_r', 'b_r')] + [('ld_hh', i32), ('ld_r', i32)] + \
                [(n, vp) for n in ('h_prev', 'c_prev', 'c', 'h', 'fake', 'save')]
@@ -219,6 +228,8 @@ SIGS = {
     'l2s_cap_att_dots_rows': (i32, [vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]),
     'l2s_cap_apply_gates_rows': (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, i32, vp]),
     'l2s_decode_pick_rows': (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    'l2s_lstm_cell_rows': (i32, [C.POINTER(LstmRows), i32, i32, i32, vp, vp]),
+    'l2s_cap_att_apply_rows': (i32, [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp]),
     'l2s_lstm_step_fwd': (i32, [vp, i32, i32, vp]),
     'l2s_lstm_step_bwd': (i32, [vp, i32, i32, vp]),
     'l2s_gru_step_fwd': (i32, [vp, i32, i32, vp]),

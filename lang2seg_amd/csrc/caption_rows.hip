@@ -5,7 +5,11 @@
 //   l2s_adaptive_pool_rows    adaptive_pool_fwd_kernel (misc_kernels.hip)
 //   l2s_cap_att_dots_rows     cap_att_dots_kernel (caption_step.hip) without the tanh copy that only backward reads
 //   l2s_cap_apply_gates_rows  cap_apply_gates_kernel (caption_step.hip) without `save` / `weight`
+//   l2s_cap_att_apply_rows    cap_att_apply_kernel (caption_step.hip) without `weight`
 //   l2s_decode_pick_rows      the greedy branch of decode_pick_kernel (decode.hip), or the log-probability of a forced token
+// The exception is l2s_lstm_cell_rows, the top-down captioner's nn.LSTMCell on rows: topdown_cell_fwd_kernel's arithmetic with the
+// products on MFMA tiles of rows (another summation order, within the forward tolerance of the single-row cell), because the single-row
+// kernel streams a whole weight matrix per row.
 // The recurrent step stays row-strided rather than one fused workgroup per row: a row reads its own patt [L][AH] and P [L][2R], 1.2 MB at
 // the production widths, and one workgroup pulls that through ONE compute unit's L2 port - at rows = 8 that is 8 of 256 ports busy for
 // about 8 us a token.  The strided grids spread every row over cdiv(L, 4) / cdiv(R, 16) workgroups and fill the device from one row on.
@@ -21,6 +25,7 @@
 namespace {
 
 constexpr int ROWS_T = 256;
+typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ bool row_live(int r, int row0, const int* count) { return !count || row0 + r < *count; }
 __device__ __forceinline__ int rbin_lo(int i, int n_in, int n_out) { return (i * n_in) / n_out; }
@@ -146,6 +151,117 @@ __global__ __launch_bounds__(256) void cap_apply_gates_rows_kernel(const float* 
   }
 }
 
+// ---------------------------------------------------------------- the top-down step on rows
+// l2s_lstm_cell_rows.  The single-row cell (topdown_cell_fwd_kernel) streams a whole weight matrix per row; here the products run as tiles
+// of the exact-fp32 MFMA (v_mfma_f32_16x16x4_f32, the lane maps of linear_nt_mfma_kernel in lang.hip: a lane holds A[l%16][l/16] and
+// B[l/16][l%16], D rows 4(l/16)+reg, column l%16), so a weight element is fetched once per tile of MT * 16 rows.  Workgroup = CELL_U = 4
+// hidden units x MT 16-row tiles: its 16 MFMA columns are the four gate rows of its units (column 4 q + u = gate q of unit u), so it owns
+// everything the cell of those units needs and finishes it after one LDS sum; its 4 waves split each segment's K.  At R = 512 that is
+// 128 workgroups x cdiv(rows, 32), each pulling 16 weight rows (98 KB of the 1536 columns) and its tile's x rows.
+struct RSeg { const float* x; int ldx; const float* w; int ld; int n; };
+struct CellR { const float* pre; int ld_pre; const float* pre2; int ld_pre2; const float* add0; const float* add1; RSeg s0, s1;
+               const float* c_prev; int ld_cp; float* c; int ld_c; float* h; int ld_h; };
+constexpr int CELL_U = 4;
+
+// p[k .. k + 3], zero at and beyond n.  VEC: n % 4 == 0 and p + k is 16-byte aligned, so the four are inside or outside together
+template <bool VEC>
+__device__ __forceinline__ float4 ld4_upto(const float* __restrict__ p, int k, int n) {
+  if (VEC) return k < n ? *(const float4*)(p + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+  return make_float4(k < n ? p[k] : 0.f, k + 1 < n ? p[k + 1] : 0.f, k + 2 < n ? p[k + 2] : 0.f, k + 3 < n ? p[k + 3] : 0.f);
+}
+// one segment's share of wave wv: acc[t] += x rows of tile t (A) . the workgroup's 16 weight rows (B).  xr[t]: the lane's x row, null
+// where that row is dead or beyond `rows` (never read: zeros); wr: the lane's weight row.
+template <int MT, bool VEC>
+__device__ __forceinline__ void cell_rows_seg(const float* const (&xr)[MT], const float* __restrict__ wr, int n, int wv, int kq, floatx4 (&acc)[MT]) {
+  const int kper = ((n + 63) / 64) * 16;                  // K range of one wave, a multiple of 16
+  const int kb = wv * kper, ke = min(n, kb + kper);
+  for (int k = kb; k < ke; k += 16) {
+    const int kk = k + 4 * kq;
+    const float4 bv = ld4_upto<VEC>(wr, kk, ke);
+    float4 av[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) av[t] = xr[t] ? ld4_upto<VEC>(xr[t], kk, ke) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t].x, bv.x, acc[t], 0, 0, 0);
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t].y, bv.y, acc[t], 0, 0, 0);
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t].z, bv.z, acc[t], 0, 0, 0);
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t].w, bv.w, acc[t], 0, 0, 0);
+    }
+  }
+}
+template <int MT, bool VEC>
+__global__ __launch_bounds__(256) void lstm_cell_rows_kernel(CellR a, int R, int rows, int row0, const int* __restrict__ count) {
+  __shared__ float red[4][MT][4][64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, j = lane & 15, kq = lane >> 4;
+  const int u0 = blockIdx.x * CELL_U, m0 = blockIdx.y * (16 * MT);
+  int nlive = rows;                                      // the live rows are the first nlive
+  if (count) { nlive = *count - row0; nlive = nlive < 0 ? 0 : (nlive > rows ? rows : nlive); }
+  if (m0 >= nlive) return;                               // (the whole workgroup: before any barrier)
+  const long wrow = (long)(j >> 2) * R + min(u0 + (j & 3), R - 1);
+  floatx4 acc[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+  if (a.s0.n > 0) {
+    const float* xr[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) { const int m = m0 + 16 * t + j; xr[t] = m < nlive ? a.s0.x + (long)m * a.s0.ldx : nullptr; }
+    cell_rows_seg<MT, VEC>(xr, a.s0.w + wrow * a.s0.ld, a.s0.n, wv, kq, acc);
+  }
+  if (a.s1.n > 0) {
+    const float* xr[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) { const int m = m0 + 16 * t + j; xr[t] = m < nlive ? a.s1.x + (long)m * a.s1.ldx : nullptr; }
+    cell_rows_seg<MT, VEC>(xr, a.s1.w + wrow * a.s1.ld, a.s1.n, wv, kq, acc);
+  }
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wv][t][r][lane] = acc[t][r];
+  __syncthreads();
+  // thread (tile t, row ml, unit u) adds the four waves' shares of its four gates in a fixed order and finishes the cell
+  if (tid < 64 * MT) {
+    const int t = tid >> 6, ml = (tid & 63) >> 2, u = tid & 3;
+    const int m = m0 + 16 * t + ml, unit = u0 + u;
+    if (m < nlive && unit < R) {
+      float g[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int at = (ml >> 2) * 16 + 4 * q + u;
+        float v = ((red[0][t][ml & 3][at] + red[1][t][ml & 3][at]) + red[2][t][ml & 3][at]) + red[3][t][ml & 3][at];
+        if (a.pre) v += a.pre[(long)m * a.ld_pre + q * R + unit];
+        if (a.pre2) v += a.pre2[(long)m * a.ld_pre2 + q * R + unit];
+        if (a.add0) v += a.add0[q * R + unit];
+        if (a.add1) v += a.add1[q * R + unit];
+        g[q] = v;
+      }
+      float act[4];
+      lstm_cell_fwd(g, a.c_prev[(long)m * a.ld_cp + unit], a.c[(long)m * a.ld_c + unit], a.h[(long)m * a.ld_h + unit], act);
+    }
+  }
+}
+
+// l2s_cap_att_apply_rows: cap_att_apply_kernel (caption_step.hip) per row, cdiv(R, 64) workgroups a row, each recomputing the row's softmax;
+// the sum over the locations in that kernel's order (4 location groups, added 0 + 1 + 2 + 3), no `weight` output
+__global__ __launch_bounds__(256) void cap_att_apply_rows_kernel(const float* __restrict__ att, const float* __restrict__ dots, float* att_res, int ld_res,
+                                                                int row0, const int* __restrict__ count, int L, int D) {
+  __shared__ float w[256];
+  __shared__ float red[4];
+  __shared__ float part[4][64];
+  const int r = blockIdx.y, tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
+  if (!row_live(r, row0, count)) return;
+  const float wt = block_softmax(dots + (long)r * 256, L, red);
+  if (tid < L) w[tid] = wt;
+  __syncthreads();
+  const int d = blockIdx.x * 64 + lane;
+  const float* ar = att + (long)r * L * D;
+  float s = 0.f;
+  if (d < D) for (int l = g; l < L; l += 4) s = fmaf(w[l], ar[(long)l * D + d], s);
+  part[g][lane] = s;
+  __syncthreads();
+  if (g == 0 && d < D) att_res[(long)r * ld_res + d] = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
+}
+
 // ---------------------------------------------------------------- l2s_decode_pick_rows
 __device__ __forceinline__ bool rows_better(float ov, int ok, float bv, int bk) {
   return ok != INT_MAX && ov == ov && (bk == INT_MAX || ov > bv || (ov == bv && ok < bk));
@@ -237,6 +353,42 @@ extern "C" int l2s_cap_apply_gates_rows(const float* P, const float* dots, const
       ld_sums < 5 * R)
     return L2S_EINVAL;
   L2S_LAUNCH(cap_apply_gates_rows_kernel, dim3(cdiv(R, 16), rows), dim3(256), 0, s, P, dots, b_a2c, sums, ld_sums, c_prev, c, h, row0, count, L, R);
+  return l2s_check_launch();
+}
+
+static bool rows_seg_ok(const l2s_rows_seg& g, int rows) {
+  return g.n == 0 || (g.n > 0 && g.x && g.w && g.ld >= g.n && (g.ldx >= g.n || rows == 1));
+}
+static bool rows_seg_vec(const l2s_rows_seg& g) {
+  return g.n == 0 || !((g.n & 3) || (g.ld & 3) || (g.ldx & 3) || ((uintptr_t)g.x & 15) || ((uintptr_t)g.w & 15));
+}
+extern "C" int l2s_lstm_cell_rows(const l2s_lstm_rows* a, int R, int rows, int row0, const int* count, hipStream_t s) {
+  if (!a || R < 1 || rows < 1 || row0 < 0 || !a->c_prev || !a->c || !a->h || !rows_seg_ok(a->seg[0], rows) || !rows_seg_ok(a->seg[1], rows) ||
+      cdiv(rows, 16) > 65535)
+    return L2S_EINVAL;
+  if (rows > 1 && (a->ld_c_prev < R || a->ld_c < R || a->ld_h < R || (a->pre && a->ld_pre != 0 && a->ld_pre < 4 * R) ||
+                   (a->pre2 && a->ld_pre2 != 0 && a->ld_pre2 < 4 * R)))
+    return L2S_EINVAL;
+  const CellR k{a->pre, a->ld_pre, a->pre2, a->ld_pre2, a->add0, a->add1,
+                RSeg{a->seg[0].x, a->seg[0].ldx, a->seg[0].w, a->seg[0].ld, a->seg[0].n},
+                RSeg{a->seg[1].x, a->seg[1].ldx, a->seg[1].w, a->seg[1].ld, a->seg[1].n},
+                a->c_prev, a->ld_c_prev, a->c, a->ld_c, a->h, a->ld_h};
+  const bool vec = rows_seg_vec(a->seg[0]) && rows_seg_vec(a->seg[1]);
+  const dim3 g1(cdiv(R, CELL_U), cdiv(rows, 16)), g2(cdiv(R, CELL_U), cdiv(rows, 32));
+  if (rows <= 16) {
+    if (vec) L2S_LAUNCH((lstm_cell_rows_kernel<1, true>), g1, dim3(256), 0, s, k, R, rows, row0, count);
+    else L2S_LAUNCH((lstm_cell_rows_kernel<1, false>), g1, dim3(256), 0, s, k, R, rows, row0, count);
+  } else {
+    if (vec) L2S_LAUNCH((lstm_cell_rows_kernel<2, true>), g2, dim3(256), 0, s, k, R, rows, row0, count);
+    else L2S_LAUNCH((lstm_cell_rows_kernel<2, false>), g2, dim3(256), 0, s, k, R, rows, row0, count);
+  }
+  return l2s_check_launch();
+}
+
+extern "C" int l2s_cap_att_apply_rows(const float* att, const float* dots, float* att_res, int ld_res, int rows, int row0, const int* count, int L,
+                                      int R, hipStream_t s) {
+  if (!att || !dots || !att_res || rows < 1 || rows > 65535 || row0 < 0 || L < 1 || L > 256 || R < 1 || ld_res < R) return L2S_EINVAL;
+  L2S_LAUNCH(cap_att_apply_rows_kernel, dim3(cdiv(R, 64), rows), dim3(256), 0, s, att, dots, att_res, ld_res, row0, count, L, R);
   return l2s_check_launch();
 }
 

@@ -4,16 +4,23 @@ decodes every row greedily; caption_score_rows scores ONE expression, teacher-fo
 cycle loss minimises for the ground-truth mask (AttModel.forward + a gather, LanguageModelCriterion's mask all ones).
 
 Two routes:
-  batched   att2in2 in the projected form (L = 196 <= 256, rnn_size <= 1024): the head as GEMMs on rows * 196 rows, then per token
-            [embedding, i2h] (greedy; scoring does both once for all n + 1 inputs) -> h2h and h2att as row-batch Linears -> the row-strided
-            attention dots and softmax + gates (csrc/caption_rows.hip) -> logit Linear -> l2s_decode_pick_rows.  8 launches a token (6 when
-            scoring) whatever `rows` and `count` are; `count` stays on the device.
-  loop      every other captioner, `net.rows_batched = False`, or shapes outside the limits: the single-mask launches of nets/decode.py row
+  batched   att2in2 in the projected form and topdown (L = 196 <= 256, rnn_size <= 1024), each through its captioner's rows_* functions
+            (nets/captioners.py); the logits and the decision (l2s_decode_pick_rows) are this file's.  Whatever `rows` and `count` are, the
+            launches per token are the same, and `count` stays on the device.
+              att2in2  the head as GEMMs on rows * 196 rows (att_embed, ctx2att, P = att . W_a2c^T), then per token [embedding, i2h]
+                       (greedy; scoring does both once for all n + 1 inputs) -> h2h and h2att as row-batch Linears -> the row-strided
+                       attention dots and softmax + gates (csrc/caption_rows.hip) -> logits -> decision: 8 launches a token, 6 when scoring.
+              topdown  the head: att_embed and ctx2att on rows * 196 rows, fc_embed and the fc product (fcrow [rows][4 rnn_size]) on rows;
+                       per token [embedding, the xt columns of att_lstm.weight_ih] (greedy; once per call when scoring) -> the attention
+                       cell (l2s_lstm_cell_rows: both products on MFMA tiles of rows and the cell in one launch) -> h2att -> attention
+                       dots -> softmax + weighted sum (l2s_cap_att_apply_rows) -> the language cell (l2s_lstm_cell_rows) -> logits ->
+                       decision: 9 launches a token, 7 when scoring.
+  loop      adaatt / adaattmo, `net.rows_batched = False`, or shapes outside the limits: the single-mask launches of nets/decode.py row
             by row (head, decode_start, T x step), the decision by l2s_decode_pick_rows on one row.  Reads `count` back once per call.
-            Slow (about rows * 3 T dependent launches) but correct for every captioner, and the cross-check of the batched route.
+            Slow (about rows * 3 T dependent launches, 5 T for topdown) but correct for every captioner, and the cross-check of the batched route.
 
-Rows are processed in chunks of at most CHUNK = 64, so the head's products (a, patt, P: 196 * 64 rows of 4 rnn_size + att_hid_size floats)
-stay near 0.1 GB at the production widths beside the chunk's 0.1 GB of features.  Every buffer is `rows.*` (the loop also uses decoding's
+Rows are processed in chunks of at most CHUNK = 64, so the head's products (a, patt, P: 196 * 64 rows of 4 rnn_size + att_hid_size floats;
+topdown has no P) stay near 0.1 GB at the production widths beside the chunk's 0.1 GB of features.  Every buffer is `rows.*` (the loop also uses decoding's
 `dec.*`): a call between a training forward and its backward leaves what that backward reads alone.  The results are the network's buffers:
 valid until the next call."""
 import numpy as np
@@ -68,9 +75,9 @@ def caption_features_rows(net, masks, rows, shape, count=None):
 
 
 def batched(net):
-    """the batched route serves this network: att2in2, projected, inside the row kernels' limits"""
-    cap = net.captioner
-    return bool(getattr(net, 'rows_batched', True)) and net.cap_model == 'att2in2' and bool(cap.proj()) and net.opt['rnn_size'] <= 1024
+    """the batched route serves this network: its captioner has the step on rows (att2in2 in the projected form, topdown) and the shapes
+    are inside the row kernels' limits (rnn_size <= 1024; L = 196 <= 256 always holds)"""
+    return bool(getattr(net, 'rows_batched', True)) and bool(net.captioner.rows_ok())
 
 
 def _start(net, what, att_feats, fc_feats, rows, count):
@@ -104,46 +111,26 @@ def _outputs(net, rows, T):
     return seq, lps, score, net.buf('rows.finished', (rows,), i32)
 
 
-def _run_batched(net, att, rows, count, T, seq, lps, score, fin, inputs=None, targets=None):
-    """inputs / targets: device int64 [T] for teacher forcing (None: greedy)"""
+def _run_batched(net, att, fc, rows, count, T, seq, lps, score, fin, inputs=None, targets=None):
+    """inputs / targets: device int64 [T] for teacher forcing (None: greedy).  The captioner's rows_* functions (nets/captioners.py) issue
+    its head and its token step; the logits and the decision are every captioner's"""
     cap = net.captioner
-    R, IE, AH = cap.dims()
-    AF, V1 = net.opt['att_feat_size'], net.opt['vocab_size'] + 1
-    pv = cap.pv
+    R, V1 = net.opt['rnn_size'], net.opt['vocab_size'] + 1
     nb = min(rows, CHUNK)
     b = lambda n, shp, zero=False: net.buf('rows.' + n, shp, f32, zero)
-    a, patt, Pm = b('a', (nb * L, R)), b('patt', (nb * L, AH)), b('P', (nb * L, 2 * R))
-    sums, att_h, dots, logits = b('sums', (nb, 5 * R)), b('att_h', (nb, AH)), b('dots', (nb, 256)), b('logits', (nb, V1))
-    xt = b('xt', (nb, IE))
+    logits = b('logits', (nb, V1))
     tokens = net.buf('rows.tokens', (nb,), i64)
     forced = inputs is not None
-    if forced:
-        # the token-only work, once for all rows: the embedding and i2h of the T inputs; h2h's bias joins each row
-        xs, bias = b('xt_all', (T, IE)), b('bias_all', (T, 5 * R))
-        O.embed_fwd(pv('embed.0.weight'), inputs, None, xs, T, IE, True)
-        cap.token_inputs(xs, bias, T)
-        for t in range(T):
-            O.add_f32(bias[t], pv('core.h2h.bias'), bias[t])
+    # the token-only work, once for all rows
+    pre = cap.rows_forced(b, inputs, T) if forced else None
     for c0 in range(0, rows, CHUNK):
         n = min(CHUNK, rows - c0)
-        # the head of n rows: att_embed (Linear + ReLU), ctx2att and P = att . W_a2c^T as GEMMs on n * 196 rows
-        net.att_embed.fwd(att[c0:c0 + n], n * L, 1, 1, a, relu=True, out_f32=True)
-        O.linear_fwd(a, pv('ctx2att.weight'), pv('ctx2att.bias'), patt, n * L, AH, R)
-        O.linear_fwd(a, pv('core.a2c.weight'), None, Pm, n * L, 2 * R, R)
-        st = [(b('h.' + k, (nb, R), True), b('c.' + k, (nb, R), True)) for k in 'ab']
+        H = cap.rows_head(b, att[c0:c0 + n], fc[c0:c0 + n] if fc is not None else None, n, nb)
+        st = cap.rows_states(b, nb)
         O.memset_zero(tokens)                                   # <bos>; a dead row's slot stays a valid index for the embedding
         for t in range(T):
-            (h0, cp), (h1, c1) = st[t & 1], st[1 - (t & 1)]
-            if forced:
-                O.linear_fwd(h0, pv('core.h2h.weight'), bias[t], sums, n, 5 * R, R)
-            else:
-                O.embed_fwd(pv('embed.0.weight'), tokens, None, xt, n, IE, True)
-                cap.token_inputs(xt, sums, n)
-                O.linear_fwd(h0, pv('core.h2h.weight'), pv('core.h2h.bias'), sums, n, 5 * R, R, accumulate=True)
-            O.linear_fwd(h0, pv('core.attention.h2att.weight'), pv('core.attention.h2att.bias'), att_h, n, AH, R)
-            O.cap_att_dots_rows(patt, att_h, pv('core.attention.alpha_net.weight'), pv('core.attention.alpha_net.bias'), n, L, AH, dots, count, c0)
-            O.cap_apply_gates_rows(Pm, dots, pv('core.a2c.bias'), sums, cp, c1, h1, n, L, R, count, c0)
-            O.linear_fwd(h1, pv('logit.weight'), pv('logit.bias'), logits, n, V1, R)
+            out = cap.rows_step(b, H, st[t & 1], st[1 - (t & 1)], n, nb, tokens, pre[t] if forced else None, count, c0)
+            O.linear_fwd(out, cap.pv('logit.weight'), cap.pv('logit.bias'), logits, n, V1, R)
             O.decode_pick_rows(logits, V1, n, t, T, fin[c0:], seq[c0:], lps[c0:], tokens, targets[t:t + 1] if forced else None, count, c0,
                                score=score[c0:])
 
@@ -176,7 +163,7 @@ def caption_decode_rows(net, att_feats, fc_feats=None, rows=None, count=None, sa
     T = int(net.opt['seq_length'])
     seq, lps, score, fin = _outputs(net, rows, T)
     if batched(net):
-        _run_batched(net, att, rows, count, T, seq, lps, score, fin)
+        _run_batched(net, att, fc, rows, count, T, seq, lps, score, fin)
     else:
         _run_loop(net, att, fc, rows, count, T, seq, lps, score, fin)
     return {'seq': seq, 'logprobs': lps}
@@ -194,7 +181,7 @@ def caption_score_rows(net, att_feats, fc_feats, tokens, rows=None, count=None):
     io = torch.tensor([[0] + toks, toks + [0]], dtype=i64).to(net.device)
     seq, lps, score, fin = _outputs(net, rows, T)
     if batched(net):
-        _run_batched(net, att, rows, count, T, seq, lps, score, fin, io[0], io[1])
+        _run_batched(net, att, fc, rows, count, T, seq, lps, score, fin, io[0], io[1])
     else:
         _run_loop(net, att, fc, rows, count, T, seq, lps, score, fin, io[1])
     return {'logprobs': lps, 'score': score}

@@ -184,6 +184,15 @@ class Captioner(object):
         self.fcrow(self.fc_embed(fc, self.db)[2], fcrow)
         return self.sentence(ad, patt, fcrow=fcrow)
 
+    # ------------------------------------------------------------------ the caption branch on rows (nets/caption_rows.py: the batched route)
+    # b(name, shape, zero=False): the route's float buffers ('rows.*'), sized for nb rows; n <= nb rows of the chunk are in use.  A captioner
+    # that serves the route has rows_forced (teacher forcing: the token-only work of the T inputs, once per call -> what rows_step takes as
+    # pre_t, per t), rows_head (per chunk), rows_states (two zeroed sets) and rows_step (one token: cur -> new, returns the outputs
+    # [nb][rnn_size]); the number of entries each issues depends neither on n nor on count[0].
+    def rows_ok(self):
+        """the batched route serves this captioner at the network's shapes (otherwise: the loop)"""
+        return False
+
 
 class Att2in2(Captioner):
     """ATT:406-466.  The recurrence as one resident launch (csrc/cap_recur.hip) where the shapes allow, else 3 launches per token in the
@@ -322,6 +331,50 @@ class Att2in2(Captioner):
         (h0, _), (c0, _), (h1, _), (c1, _) = cur['h'], cur['c'], new['h'], new['c']
         for r in range(B):
             self.token(H, sums[r], h0[r], c0[r], h1[r], c1[r], att_h[r], tanh_ws, wgt, save, scr)
+        return h1
+
+    # ---- on rows: the projected form.  8 launches a token with the logits and the decision (6 when scoring)
+    def rows_ok(self):
+        return bool(self.proj()) and self.net.opt['rnn_size'] <= 1024
+
+    def rows_forced(self, b, inputs, T):
+        """the embedding and i2h of the T inputs; h2h's bias joins each row"""
+        R, IE, AH = self.dims()
+        xs, bias = b('xt_all', (T, IE)), b('bias_all', (T, 5 * R))
+        O.embed_fwd(self.pv('embed.0.weight'), inputs, None, xs, T, IE, True)
+        self.token_inputs(xs, bias, T)
+        for t in range(T):
+            O.add_f32(bias[t], self.pv('core.h2h.bias'), bias[t])
+        return bias
+
+    def rows_head(self, b, att, fc, n, nb):
+        """att_embed (Linear + ReLU), ctx2att and P = att . W_a2c^T as GEMMs on n * 196 rows"""
+        R, IE, AH = self.dims()
+        a, patt, Pm = b('a', (nb * L, R)), b('patt', (nb * L, AH)), b('P', (nb * L, 2 * R))
+        self.net.att_embed.fwd(att, n * L, 1, 1, a, relu=True, out_f32=True)
+        O.linear_fwd(a, self.pv('ctx2att.weight'), self.pv('ctx2att.bias'), patt, n * L, AH, R)
+        O.linear_fwd(a, self.pv('core.a2c.weight'), None, Pm, n * L, 2 * R, R)
+        return dict(patt=patt, Pm=Pm)
+
+    def rows_states(self, b, nb):
+        R = self.net.opt['rnn_size']
+        return [(b('h.' + k, (nb, R), True), b('c.' + k, (nb, R), True)) for k in 'ab']
+
+    def rows_step(self, b, H, cur, new, n, nb, tokens, pre_t, count, row0):
+        R, IE, AH = self.dims()
+        pv = self.pv
+        sums, att_h, dots = b('sums', (nb, 5 * R)), b('att_h', (nb, AH)), b('dots', (nb, 256))
+        (h0, cp), (h1, c1) = cur, new
+        if pre_t is not None:
+            O.linear_fwd(h0, pv('core.h2h.weight'), pre_t, sums, n, 5 * R, R)
+        else:
+            xt = b('xt', (nb, IE))
+            O.embed_fwd(pv('embed.0.weight'), tokens, None, xt, n, IE, True)
+            self.token_inputs(xt, sums, n)
+            O.linear_fwd(h0, pv('core.h2h.weight'), pv('core.h2h.bias'), sums, n, 5 * R, R, accumulate=True)
+        O.linear_fwd(h0, pv('core.attention.h2att.weight'), pv('core.attention.h2att.bias'), att_h, n, AH, R)
+        O.cap_att_dots_rows(H['patt'], att_h, pv('core.attention.alpha_net.weight'), pv('core.attention.alpha_net.bias'), n, L, AH, dots, count, row0)
+        O.cap_apply_gates_rows(H['Pm'], dots, pv('core.a2c.bias'), sums, cp, c1, h1, n, L, R, count, row0)
         return h1
 
 
@@ -467,6 +520,64 @@ class TopDown(Captioner):
         for r in range(B):
             self.token(H, xpre[r], hl0[r], cl0[r], ca0[r], lin0[r][R:], hl1[r], cl1[r], ca1[r], lin1[r], att_h[r], tanh_ws, wgt, dots, act, act)
         return hl1
+
+    # ---- on rows: `token`'s five launches with the two cells as l2s_lstm_cell_rows (a weight element fetched once per tile of rows, not
+    # once per row) and the attention row-strided.  9 launches a token with the logits and the decision (7 when scoring)
+    def rows_ok(self):
+        return self.net.opt['rnn_size'] <= 1024
+
+    def rows_forced(self, b, inputs, T):
+        """the embedding and the xt columns of att_lstm.weight_ih (+ bias_ih) of the T inputs: step t takes row t for every row"""
+        R, IE, AH = self.dims()
+        xs, pre = b('xt_all', (T, IE)), b('xpre_all', (T, 4 * R))
+        O.embed_fwd(self.pv('embed.0.weight'), inputs, None, xs, T, IE, True)
+        self.token_inputs(xs, pre, T)
+        return pre
+
+    def rows_head(self, b, att, fc, n, nb):
+        """att_embed (Linear + ReLU) and ctx2att as GEMMs on n * 196 rows; fc_embed (Linear + ReLU) and the fc product (`fcrow` per row:
+        the fc columns of att_lstm.weight_ih + bias_hh) on n rows.  No projected attention: the top-down attention reads `a` itself"""
+        R, IE, AH = self.dims()
+        FC = self.net.opt['fc_feat_size']
+        a, patt, fce, fcrow = b('a', (nb * L, R)), b('patt', (nb * L, AH)), b('fce', (nb, R)), b('fcrow', (nb, 4 * R))
+        self.net.att_embed.fwd(att, n * L, 1, 1, a, relu=True, out_f32=True)
+        O.linear_fwd(a, self.pv('ctx2att.weight'), self.pv('ctx2att.bias'), patt, n * L, AH, R)
+        if fc.dtype != f32:
+            fc32 = b('fc32', (nb, FC)); O.cast(fc, fc32)
+        else:
+            fc32 = fc
+        O.linear_fwd(fc32, self.pv('fc_embed.0.weight'), self.pv('fc_embed.0.bias'), fce, n, R, FC, act=1)
+        O.linear_fwd(fce, self.pv('core.att_lstm.weight_ih')[R:], self.pv('core.att_lstm.bias_hh'), fcrow, n, 4 * R, R, ldw=IE + 2 * R)
+        return dict(a=a, patt=patt, fcrow=fcrow)
+
+    def rows_states(self, b, nb):
+        """two sets of hl | cl | ca [nb][R] and lin [nb][2R] = [att_res | h_att] side by side: one launch clears both"""
+        R = self.net.opt['rnn_size']
+        st = b('td_state', (2, 5 * nb * R), True)
+        return [dict(zip(('hl', 'cl', 'ca', 'lin'), s.split([nb * R, nb * R, nb * R, 2 * nb * R]))) for s in st]
+
+    def rows_step(self, b, H, cur, new, n, nb, tokens, pre_t, count, row0):
+        R, IE, AH = self.dims()
+        Ka = IE + 2 * R
+        pv = self.pv
+        wa_ih, wa_hh, wl_ih, wl_hh, bl_ih, bl_hh, h2w, h2b, aw, ab = (pv('core.' + k) for k in self.w_keys)
+        att_h, dots = b('att_h', (nb, AH)), b('dots', (nb, 256))
+        if pre_t is not None:
+            xpre, ld_pre = pre_t, 0
+        else:
+            xt, xpre, ld_pre = b('xt', (nb, IE)), b('xpre', (nb, 4 * R)), 4 * R
+            O.embed_fwd(pv('embed.0.weight'), tokens, None, xt, n, IE, True)
+            self.token_inputs(xt, xpre, n)
+        lin0, lin1 = cur['lin'], new['lin']
+        h_att = lin1[R:]
+        O.lstm_cell_rows(xpre, None, None, [(cur['hl'], R, wa_ih, Ka, R), (lin0[R:], 2 * R, wa_hh, R, R)], cur['ca'], new['ca'], h_att, n, R, count, row0,
+                         ld_pre=ld_pre, pre2=H['fcrow'], ld_h=2 * R)
+        O.linear_fwd(h_att, h2w, h2b, att_h, n, AH, R, ldx=2 * R)
+        O.cap_att_dots_rows(H['patt'], att_h, aw, ab, n, L, AH, dots, count, row0)
+        O.cap_att_apply_rows(H['a'], dots, lin1, n, L, R, count, row0, ld_res=2 * R)
+        O.lstm_cell_rows(None, bl_ih, bl_hh, [(lin1, 2 * R, wl_ih, 2 * R, 2 * R), (cur['hl'], R, wl_hh, R, R)], cur['cl'], new['cl'], new['hl'], n, R,
+                         count, row0)
+        return new['hl']
 
 
 class AdaAtt(Captioner):

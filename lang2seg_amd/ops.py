@@ -855,6 +855,41 @@ def cap_apply_gates_rows(P, dots, b_a2c, sums, c_prev, c, h, rows, L, R, count=N
          int(rows), int(row0), ptr(count), L, R, stream())
 
 
+def lstm_cell_rows(pre, add0, add1, segs, c_prev, c, h, rows, R, count=None, row0=0, ld_pre=None, pre2=None, ld_pre2=None, ld_c_prev=None,
+                   ld_c=None, ld_h=None):
+    """one nn.LSTMCell step on rows (csrc/caption_rows.hip): gates[r] = pre[r * ld_pre] + pre2[r * ld_pre2] + add0 + add1 + sum over segs
+    (x, ldx, w, ld, n) of w[4R][:n] . x[r * ldx][:n], with w a column block (leading dimension ld) of a wider matrix; writes c[r * ld_c]
+    and h[r * ld_h].  ld_pre = 0: one row of pre for all rows.  Up to two segments; None entries are skipped.  Every tensor is the flat
+    view that starts at its first element (h inside a wider row: array.view(-1)[offset:])."""
+    _rows_count('lstm_cell_rows', rows, row0, count)
+    G = 4 * R
+    ld_pre, ld_pre2 = (G if v is None else int(v) for v in (ld_pre, ld_pre2))
+    ld_c_prev, ld_c, ld_h = (R if v is None else int(v) for v in (ld_c_prev, ld_c, ld_h))
+    span = lambda ld, w: (rows - 1) * ld + w
+    segs = [sg for sg in segs if sg is not None]
+    if len(segs) > 2 or R < 1 or min(ld_c_prev, ld_c, ld_h) < R or \
+            any(p is not None and (0 < ld < G or ld < 0 or p.numel() < span(ld, G)) for p, ld in ((pre, ld_pre), (pre2, ld_pre2))) or \
+            any(v is not None and v.numel() < G for v in (add0, add1)) or \
+            c_prev.numel() < span(ld_c_prev, R) or c.numel() < span(ld_c, R) or h.numel() < span(ld_h, R) or \
+            any(n < 1 or ld < n or ldx < n or x.numel() < span(ldx, n) or w.numel() < (G - 1) * ld + n for x, ldx, w, ld, n in segs):
+        raise ValueError('lstm_cell_rows: a buffer is smaller than rows = %d, R = %d and its leading dimension ask, or more than two segments' % (rows, R))
+    a = _lib.LstmRows()
+    a.pre, a.ld_pre, a.pre2, a.ld_pre2, a.add0, a.add1 = ptr(pre), ld_pre, ptr(pre2), ld_pre2, ptr(add0), ptr(add1)
+    a.c_prev, a.ld_c_prev, a.c, a.ld_c, a.h, a.ld_h = ptr(c_prev), ld_c_prev, ptr(c), ld_c, ptr(h), ld_h
+    for q, (x, ldx, w, ld, n) in zip(a.seg, segs):
+        q.x, q.ldx, q.w, q.ld, q.n = ptr(x), int(ldx), ptr(w), int(ld), int(n)
+    call('l2s_lstm_cell_rows', C.byref(a), int(R), int(rows), int(row0), ptr(count), stream())
+
+
+def cap_att_apply_rows(att, dots, att_res, rows, L, R, count=None, row0=0, ld_res=None):
+    """att_res[r * ld_res][:R] = cap_att_apply_fwd per row of att [rows][L][R] and dots [rows][256], without the weights"""
+    _rows_count('cap_att_apply_rows', rows, row0, count)
+    ld = R if ld_res is None else int(ld_res)
+    if att.numel() < rows * L * R or dots.numel() < rows * 256 or L > 256 or ld < R or att_res.numel() < (rows - 1) * ld + R:
+        raise ValueError('cap_att_apply_rows: a buffer is smaller than rows = %d asks, or L = %d > 256' % (rows, L))
+    call('l2s_cap_att_apply_rows', ptr(att), ptr(dots), ptr(att_res), ld, int(rows), int(row0), ptr(count), L, R, stream())
+
+
 def decode_pick_rows(logits, V1, rows, t, T, finished, seq, logprobs, next_token, forced=None, count=None, row0=0, ld_logits=None, score=None):
     """per row of logits f32 [rows][V1]: the greedy decision of decode_pick, or with forced (device int64 [1]) that token and its
     log-probability; finished int32 [rows], seq int64 [rows][T], logprobs f32 [rows][T] (column t), next_token int64 [rows], score f32 [rows]

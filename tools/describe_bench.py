@@ -1,13 +1,18 @@
 #!/usr/bin/env python
 """Device time of describing and of scoring every detection of one sentence (nets/caption_rows.py) on the full-size ResNet-101 'cycle'
-network (initial weights, bf16, a 600 x 1000 SyntheticLoader image, canvases 375 x 625, att2in2 at the production widths), for count = 1,
-8 and 64 live rows of cap = 64 (and count = 1 of cap = 128: what the head GEMMs on unused rows cost), by HIP events.  Three paths, timed
-in turn inside one process, `reps` rounds, the median reported:
-    batched   caption_features_rows + caption_decode_rows / caption_score_rows, the batched route (count stays on the device)
+network (initial weights, bf16, a 600 x 1000 SyntheticLoader image, canvases 375 x 625, --caption_model att2in2 or topdown at the
+production widths), for count = 1, 8 and 64 live rows of cap = 64 (and count = 1 of cap = 128: what the head GEMMs on unused rows cost),
+by HIP events.  Three paths, timed in turn inside one process, `reps` rounds, the median reported:
+    batched   caption_features_rows + caption_decode_rows / caption_score_rows, the batched route where the captioner has one, else the
+              loop (count stays on the device on the batched route)
     loop      the same entry points with net.rows_batched = False: the single-mask launches row by row
     per_mask  what the tree offered before: per mask l2s_mask_resize_nearest + caption_features(mask) + caption_decode (one read-back each);
               it has no score, so it is the yardstick of both
-Each timing includes the features.  Prints one JSON line."""
+Each timing includes the features.  --cells 1 adds `cells`: one nn.LSTMCell step of the top-down attention cell at
+rnn_size = input_encoding_size = 512 on 1, 8 and 64 rows, as l2s_lstm_cell_rows, as the existing launches it stands for on rows (two
+l2s_linear_fwd + l2s_lstm_cell_fwd per row) and as l2s_topdown_cell_fwd per row; per path the time of CELL_CALLS steps issued back to
+back between two events, over CELL_CALLS (where a kernel is shorter than the host takes to issue it, that is the issue rate).
+Prints one JSON line."""
 import argparse
 import json
 import os.path as osp
@@ -31,10 +36,54 @@ def _once_us(fn):
     return e0.elapsed_time(e1) * 1000.0
 
 
+CELL_CALLS = 20
+
+
+def cells_us(O, reps):
+    """{'rows<n>': {path + '_us': the median time of one step}}"""
+    R = IE = 512
+    Ka, G = IE + 2 * R, 4 * R
+    g = torch.Generator(device='cuda').manual_seed(5)
+    rn = lambda *shp: torch.randn(*shp, generator=g, device='cuda')
+    un = lambda *shp: (torch.rand(*shp, generator=g, device='cuda') * 2 - 1) / float(np.sqrt(R))      # (as nn.LSTMCell draws its weights)
+    w_ih, w_hh = un(G, Ka), un(G, R)
+    out = {}
+    for rows in (1, 8, 64):
+        pre, fcrow, hl, lin0, ca = rn(rows, G), rn(rows, G), rn(rows, R) * 0.5, rn(rows, 2 * R) * 0.5, rn(rows, R)
+        ca1, lin1, h1, gates, act = (torch.empty(s, device='cuda') for s in ((rows, R), (rows, 2 * R), (rows, R), (rows, G), (G,)))
+        ha0 = lin0.view(-1)[R:]
+
+        def fused():
+            O.lstm_cell_rows(pre, None, None, [(hl, R, w_ih, Ka, R), (ha0, 2 * R, w_hh, R, R)], ca, ca1, lin1.view(-1)[R:], rows, R, pre2=fcrow,
+                             ld_h=2 * R)
+
+        def composed():
+            O.linear_fwd(hl, w_ih, None, gates, rows, G, R, ldw=Ka)
+            O.linear_fwd(ha0, w_hh, None, gates, rows, G, R, accumulate=True, ldx=2 * R)
+            for r in range(rows):
+                O.lstm_cell_fwd(gates[r], ca[r], ca1[r], h1[r], act, R)
+
+        def per_row():
+            for r in range(rows):
+                O.topdown_cell_fwd(pre[r], fcrow[r], None, [(hl[r], w_ih, Ka, R), (lin0[r][R:], w_hh, R, R)], ca[r], ca1[r], h1[r], act, R)
+
+        paths = {'lstm_cell_rows': fused, 'linear2_plus_cell_per_row': composed, 'topdown_cell_fwd_per_row': per_row}
+        times = {k: [] for k in paths}
+        for fn in paths.values():
+            fn()
+        for _ in range(reps):
+            for k, fn in paths.items():
+                times[k].append(_once_us(lambda: [fn() for _ in range(CELL_CALLS)]) / CELL_CALLS)
+        out['rows%d' % rows] = {k + '_us': float(np.median(v)) for k, v in times.items()}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--dtype', default='bf16'); ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--counts', default='1,8,64'); ap.add_argument('--out', default=None, help='also write the JSON result to this file')
+    ap.add_argument('--caption_model', default='att2in2', choices=['att2in2', 'topdown'])
+    ap.add_argument('--cells', type=int, default=0, help='1: also time one LSTMCell step on rows three ways (see above)')
     a = ap.parse_args()
     from lang2seg_amd import ops as O
     from lang2seg_amd.model.config import cfg, cfg_from_file
@@ -46,7 +95,7 @@ def main():
     T, V = 10, 1999
     b = SyntheticLoader(num_images=1, sents_per_image=1, H=600, W=1000, T=T, vocab_size=V, seed=1234)._image(0)
     opt = parse_opt([])
-    opt.update(vocab_size=V, C4_feat_dim=1024, seq_length=T)
+    opt.update(vocab_size=V, C4_feat_dim=1024, seq_length=T, caption_model=a.caption_model)
     if osp.exists(osp.join(ROOT, 'experiments/cfgs/res101.yml')):
         cfg_from_file(osp.join(ROOT, 'experiments/cfgs/res101.yml'))
     cfg.COMPUTE_DTYPE = a.dtype
@@ -102,6 +151,8 @@ def main():
             for k, fn in paths.items():                             # in turn: a drift of the clocks meets every path alike
                 times[k].append(_once_us(fn))
         res['rows']['cap%d_count%d' % (cap, n)] = {k + '_us': float(np.median(v)) for k, v in times.items()}
+    if a.cells:
+        res['cells'] = dict(rnn_size=512, input_encoding_size=512, calls_per_timing=CELL_CALLS, rows=cells_us(O, a.reps))
     if a.out:
         with open(a.out, 'w') as f:
             json.dump(res, f, indent=1)
