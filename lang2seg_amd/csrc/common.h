@@ -18,6 +18,8 @@ typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
+// half h (0 = low, 1 = high) of a 32-bit word that holds two bf16 values
+__device__ __forceinline__ float bf2f_x2(uint32_t w, int h) { return __uint_as_float(h ? (w & 0xFFFF0000u) : (w << 16)); }
 __device__ __forceinline__ bf16_t f2bf(float f) {
   __bf16 b = (__bf16)f;  // v_cvt_pk_bf16_f32: RNE, NaN stays NaN
   return __builtin_bit_cast(uint16_t, b);

@@ -23,6 +23,7 @@
 #include "roi_sample.h"
 #include "../../include/lang2seg_hip.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -46,22 +47,85 @@ template <> struct Mma<float> {
 constexpr int ROWB = 128;        // bytes of K per LDS row per slice
 constexpr int LROW = ROWB + 16;  // padded LDS row
 
-// ---- branch-free epilogue (all row pitches and Cout multiples of 4, extents < 2 GiB): every bias / residual / mask
-// operand of the wave's TM x TN sub-tiles is requested before the first use (buffer loads; out-of-range rows and
-// channels carry offset 0x80000000, so loads return 0 and stores are dropped), instead of one dependent HBM round trip
-// per sub-tile ----
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
+constexpr unsigned NOPE = 0x80000000u;   // buffer offset past every range: loads return 0, stores are dropped
+
+// XCD-aware tile order (1-D grid): consecutive workgroup ids are dealt round-robin over the 8 XCDs, so id % 8 labels
+// the XCD.  The tile list is cut into 8 contiguous chunks, one per XCD, ordered so that a chunk's operands fit the
+// XCD's 4 MiB L2 (xcd_mode 0: M-chunks, n fastest -> A tile reused across its n-tiles, all of W resident;
+// xcd_mode 1: N-chunks, m fastest -> one W column block resident, A streamed).  Speed only, never correctness.
+__device__ __forceinline__ void igemm_tile_of(int L, int MT, int NT, int xcd_mode, int& mt, int& nt) {
+  const int G = MT * NT, x = L & 7, slot = L >> 3, q = G >> 3, r = G & 7;
+  const int t = x * q + min(x, r) + slot;
+  if (xcd_mode == 0) { mt = t / NT; nt = t - mt * NT; } else { nt = t / MT; mt = t - nt * MT; }
+}
+
+// buffer resource over the whole 31-bit range behind ptr (behind fallback where ptr is null: such an operand is never addressed in range)
+__device__ __forceinline__ auto whole_rsrc(const void* ptr, const void* fallback = nullptr) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(ptr ? ptr : fallback), 0, 0x7FFFFFFF, 0x00020000);
+}
+
+// plain row-major output (no pixel shuffle, no strided scatter) whose y / add / ref rows lie within 31 bits of bf16 bytes
+__host__ __device__ inline bool igemm_rows31(const l2s_conv_desc& d, long M) {
+  return !(d.flags & (L2S_CONV_DECONV2X2 | L2S_CONV_SCATTER)) &&
+         M * d.ldy * 2 < (1L << 31) && (!d.add || M * d.ldadd * 2 < (1L << 31)) && (!d.ref || M * d.ldref * 2 < (1L << 31));
+}
+// the launches that may take an LDS-staged epilogue (whole-row 16-byte accesses): igemm_rows31, every pitch and Cout a multiple of 8,
+// y / add / ref / bias 16-byte aligned.  The kernels and conv_plan() call this one predicate.
+__host__ __device__ inline bool igemm_plain(const l2s_conv_desc& d, long M) {
+  return igemm_rows31(d, M) && !(d.ldy & 7) && !(d.ldadd & 7) && !(d.ldref & 7) && !(d.Cout & 7) &&
+         !((uintptr_t)d.y & 15) && !((uintptr_t)d.add & 15) && !((uintptr_t)d.ref & 15) && !((uintptr_t)d.bias & 15);
+}
+
+// ---- the epilogue's arithmetic behind the bias, once: + residual, ReLU, ReLU-mask (0 where !(ref > 0)), all in fp32; igemm_pack_bf
+// then rounds once.  The N residual / mask values of v are one float (N = 1), fp32 words (F32) or bf16 pairs (N / 2 words).
+// igemm_finish takes them in registers; igemm_finish_from takes two callables and fetches an operand only where p.add / p.ref is set ----
+template <bool F32, typename V>
+__device__ __forceinline__ float epi_elem(const V& q, int e) {
+  if constexpr (std::is_same<V, float>::value) return q;
+  else if constexpr (F32) return __uint_as_float(q[e]);
+  else return bf2f_x2(q[e >> 1], e & 1);
+}
+template <int N, bool F32, typename FA, typename FR>
+__device__ __forceinline__ void igemm_finish_from(const l2s_conv_desc& p, float (&v)[N], FA get_add, FR get_ref) {
+  if (p.add) {
+    const auto aq = get_add();
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] += epi_elem<F32>(aq, e);
+  }
+  if (p.flags & L2S_CONV_RELU) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] = fmaxf(v[e], 0.f);
+  }
+  if (p.ref) {
+    const auto rq = get_ref();
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] = epi_elem<F32>(rq, e) > 0.f ? v[e] : 0.f;       // (a select: NaN and -0 mask like 0)
+  }
+}
+template <int N, bool F32, typename VA, typename VR>
+__device__ __forceinline__ void igemm_finish(const l2s_conv_desc& p, float (&v)[N], const VA& aq, const VR& rq) {
+  igemm_finish_from<N, F32>(p, v, [&] { return aq; }, [&] { return rq; });
+}
+__device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) { return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16); }
+template <typename V, int N>
+__device__ __forceinline__ V igemm_pack_bf(const float (&v)[N]) {
+  V pk;
+#pragma unroll
+  for (int e = 0; e < N / 2; ++e) pk[e] = pack_bf2(v[2 * e], v[2 * e + 1]);
+  return pk;
+}
+
+// ---- branch-free epilogue (all row pitches and Cout multiples of 4, extents < 2 GiB): every bias / residual / mask
+// operand of the wave's TM x TN sub-tiles is requested before the first use (buffer loads; out-of-range rows and
+// channels carry offset NOPE), instead of one dependent HBM round trip per sub-tile ----
 template <typename T, int TM, int TN, int WM, int WN, bool OUTF32>
 __device__ __forceinline__ void igemm_epilogue_fast(const l2s_conv_desc& p, f32x4 (&acc)[TM][TN], int m0, int n0, int wm, int wn, int fr, int fg, int M) {
-  constexpr unsigned NOPE = 0x80000000u;
   constexpr int ES = (int)sizeof(T), OS = (OUTF32 || sizeof(T) == 4) ? 4 : 2;
   const int ohw = p.OH * p.OW;
   const int Cq = (p.flags & L2S_CONV_DECONV2X2) ? (p.Cout >> 2) : p.Cout;
-  const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, 0x7FFFFFFF, 0x00020000);
-  const auto radd = __builtin_amdgcn_make_buffer_rsrc((void*)(p.add ? p.add : p.y), 0, 0x7FFFFFFF, 0x00020000);
-  const auto rref = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ref ? p.ref : p.y), 0, 0x7FFFFFFF, 0x00020000);
-  const auto rbias = __builtin_amdgcn_make_buffer_rsrc((void*)(p.bias ? (const void*)p.bias : (const void*)p.y), 0, 0x7FFFFFFF, 0x00020000);
+  const auto ry = whole_rsrc(p.y), radd = whole_rsrc(p.add, p.y), rref = whole_rsrc(p.ref, p.y), rbias = whole_rsrc(p.bias, p.y);
   int orow[TM][TN], ocol[TM][TN]; bool ok[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
@@ -114,39 +178,68 @@ __device__ __forceinline__ void igemm_epilogue_fast(const l2s_conv_desc& p, f32x
         else { const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(rref, o, 0, 0); rv[i][j] = (u32x4v){t.x, t.y, 0u, 0u}; }
       }
   }
-  auto unpack = [](const u32x4v& q, float (&f)[4]) {
-    if (ES == 4) { f[0] = __uint_as_float(q.x); f[1] = __uint_as_float(q.y); f[2] = __uint_as_float(q.z); f[3] = __uint_as_float(q.w); }
-    else { f[0] = __uint_as_float(q.x << 16); f[1] = __uint_as_float(q.x & 0xFFFF0000u); f[2] = __uint_as_float(q.y << 16); f[3] = __uint_as_float(q.y & 0xFFFF0000u); }
-  };
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
       if (p.bias) { v[0] += bv[j][0]; v[1] += bv[j][1]; v[2] += bv[j][2]; v[3] += bv[j][3]; }
-      if (p.add) { float a[4]; unpack(av[i][j], a); v[0] += a[0]; v[1] += a[1]; v[2] += a[2]; v[3] += a[3]; }
-      if (p.flags & L2S_CONV_RELU) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-      if (p.ref) {
-        float r[4]; unpack(rv[i][j], r);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) if (!(r[e] > 0.f)) v[e] = 0.f;
-      }
+      igemm_finish<4, ES == 4>(p, v, av[i][j], rv[i][j]);
       const unsigned o = ok[i][j] ? (unsigned)((orow[i][j] * p.ldy + ocol[i][j]) * OS) : NOPE;
       if (OS == 4) {
         __builtin_amdgcn_raw_buffer_store_b128((u32x4v){__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])}, ry, o, 0, 0);
       } else {
-        u32x2 pk;
-        pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-        pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-        __builtin_amdgcn_raw_buffer_store_b64(pk, ry, o, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(igemm_pack_bf<u32x2>(v), ry, o, 0, 0);
       }
     }
 }
 
+// ---- the chunk map of the LDS-staged epilogues: thread tid of NT owns chunks tid + NT k (k < IT) of a ROWS x BN tile, 8 channels each,
+// so BN / 8 lanes cover one output row.  at() gives chunk k's row m and column n of the matrix and whether it is inside the tile, the tile's
+// first RLIM rows and the matrix ----
+template <int ROWS, int NT, int BN, int RLIM = ROWS>
+struct EpiChunks {
+  static constexpr int CPR = BN / 8, CH = ROWS * CPR, IT = (CH + NT - 1) / NT;
+  static __device__ __forceinline__ bool at(const l2s_conv_desc& p, int m0, int n0, int M, int tid, int k, int& m, int& n) {
+    const int c = tid + NT * k, row = c / CPR;
+    m = m0 + row; n = n0 + (c % CPR) * 8;
+    return c < CH && (RLIM >= ROWS || row < RLIM) && m < M && n < p.Cout;
+  }
+};
+// requests the residual / ReLU-mask operands of this thread's chunks
+template <int ROWS, int NT, int BN, int RLIM = ROWS>
+__device__ __forceinline__ void igemm_epilogue_prefetch(const l2s_conv_desc& p, int m0, int n0, int M, int tid, u32x4v* av, u32x4v* rv) {
+  typedef EpiChunks<ROWS, NT, BN, RLIM> C;
+  const auto radd = whole_rsrc(p.add, p.y), rref = whole_rsrc(p.ref, p.y);
+#pragma unroll
+  for (int k = 0; k < C::IT; ++k) {
+    int m, n;
+    const bool ok = C::at(p, m0, n0, M, tid, k, m, n);
+    if (p.add) av[k] = __builtin_amdgcn_raw_buffer_load_b128(radd, ok ? (unsigned)((m * p.ldadd + n) * 2) : NOPE, 0, 0);
+    if (p.ref) rv[k] = __builtin_amdgcn_raw_buffer_load_b128(rref, ok ? (unsigned)((m * p.ldref + n) * 2) : NOPE, 0, 0);
+  }
+}
+// finishes and stores this thread's chunks of the staged fp32 tile st (row pitch BN + 4 floats: consecutive rows shifted by 4 banks)
+template <int ROWS, int NT, int BN, int RLIM = ROWS>
+__device__ __forceinline__ void igemm_staged_store(const l2s_conv_desc& p, const float* st, int m0, int n0, int M, int tid, const u32x4v* av, const u32x4v* rv) {
+  typedef EpiChunks<ROWS, NT, BN, RLIM> C;
+  constexpr int LDW = BN + 4;
+  const auto ry = whole_rsrc(p.y);
+#pragma unroll
+  for (int k = 0; k < C::IT; ++k) {
+    int m, n;
+    const bool ok = C::at(p, m0, n0, M, tid, k, m, n);
+    const int c = min(tid + NT * k, C::CH - 1), row = c / C::CPR, col = (c % C::CPR) * 8;
+    const f32x4 lo = *(const f32x4*)(st + row * LDW + col), hi = *(const f32x4*)(st + row * LDW + col + 4);
+    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    igemm_finish<8, false>(p, v, av[k], rv[k]);
+    __builtin_amdgcn_raw_buffer_store_b128(igemm_pack_bf<u32x4v>(v), ry, ok ? (unsigned)((m * p.ldy + n0 + col) * 2) : NOPE, 0, 0);
+  }
+}
+
 // ---- LDS-staged epilogue of the 128x128 bf16 tile (4 waves as 2 x 2, wave tile 64 x 64): the MFMA layout gives a lane 4 channels of 16
 // different pixels, i.e. 8-byte accesses in 32-byte runs to the output, the residual and the ReLU-mask operand.  Staging the fp32 tile
-// (+ bias) through LDS, 64 rows at a time, turns them into 16-byte accesses that cover whole 256-byte rows.  Same arithmetic order as
-// igemm_epilogue_fast (bias, residual, ReLU, mask in fp32, one rounding). ----
+// (+ bias) through LDS, 64 rows at a time, turns them into 16-byte accesses that cover whole 256-byte rows. ----
 template <int TM, int TN, int WM, int WN, int WGM, int NT, int BN, int PASSES>
 __device__ __forceinline__ void igemm_epilogue_lds128(const l2s_conv_desc& p, f32x4 (&acc)[TM][TN], int m0, int n0, int wm, int wn, int fr, int fg, int M, char* smem,
                                                       const u32x4v* pre_add = nullptr, const u32x4v* pre_ref = nullptr, const f32x4* pre_bias = nullptr) {
@@ -154,15 +247,11 @@ __device__ __forceinline__ void igemm_epilogue_lds128(const l2s_conv_desc& p, f3
   // loop with igemm_epilogue_prefetch (same chunk map), so that their latency does not sit between the last MFMA and the stores
   // (tile width BN = WGN x WN; PASSES passes of RP rows: the waves whose rows fall into pass h stage their sub-tiles, then all NT threads
   // store them; one pass when the whole fp32 tile fits the kernel's LDS)
-  constexpr int LDW = BN + 4;                                // floats per staged row (+ 4: shifts consecutive rows by 4 banks)
-  constexpr int RP = WM * WGM / PASSES, CPR = BN / 8;        // rows per pass, 8-channel chunks per row
-  constexpr int CH = RP * CPR, IT = (CH + NT - 1) / NT;      // chunks of one pass, chunks per thread
+  constexpr int LDW = BN + 4;                                // floats per staged row
+  constexpr int RP = WM * WGM / PASSES;                      // rows per pass
+  constexpr int IT = EpiChunks<RP, NT, BN>::IT;              // chunks per thread and pass
   static_assert((WM * WGM) % PASSES == 0 && RP % WM == 0, "passes");
-  constexpr unsigned NOPE = 0x80000000u;
   float* st = (float*)smem;
-  const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, 0x7FFFFFFF, 0x00020000);
-  const auto radd = __builtin_amdgcn_make_buffer_rsrc((void*)(p.add ? p.add : p.y), 0, 0x7FFFFFFF, 0x00020000);
-  const auto rref = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ref ? p.ref : p.y), 0, 0x7FFFFFFF, 0x00020000);
   const int tid = threadIdx.x;
   f32x4 bv[TN];
 #pragma unroll
@@ -187,65 +276,10 @@ __device__ __forceinline__ void igemm_epilogue_lds128(const l2s_conv_desc& p, f3
         }
     }
     __syncthreads();
-    // RP rows x CPR chunks of 8 channels; CPR lanes cover one output row of the tile
     u32x4v av[IT], rv[IT];
-    unsigned off[IT];
-#pragma unroll
-    for (int k = 0; k < IT; ++k) {
-      const int c = tid + NT * k, row = c / CPR, col = (c % CPR) * 8;
-      const int m = m0 + h * RP + row, n = n0 + col;
-      const bool ok = c < CH && m < M && n < p.Cout;
-      off[k] = ok ? (unsigned)m : NOPE;
-      if (PASSES == 1 && pre_add) { if (p.add) av[k] = pre_add[k]; }
-      else if (p.add) av[k] = __builtin_amdgcn_raw_buffer_load_b128(radd, ok ? (unsigned)((m * p.ldadd + n) * 2) : NOPE, 0, 0);
-      if (PASSES == 1 && pre_ref) { if (p.ref) rv[k] = pre_ref[k]; }
-      else if (p.ref) rv[k] = __builtin_amdgcn_raw_buffer_load_b128(rref, ok ? (unsigned)((m * p.ldref + n) * 2) : NOPE, 0, 0);
-    }
-#pragma unroll
-    for (int k = 0; k < IT; ++k) {
-      const int c = min(tid + NT * k, CH - 1), row = c / CPR, col = (c % CPR) * 8;
-      const f32x4 lo = *(const f32x4*)(st + row * LDW + col), hi = *(const f32x4*)(st + row * LDW + col + 4);
-      float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      if (p.add) {
-        const unsigned w[4] = {av[k].x, av[k].y, av[k].z, av[k].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { v[2 * e] += __uint_as_float(w[e] << 16); v[2 * e + 1] += __uint_as_float(w[e] & 0xFFFF0000u); }
-      }
-      if (p.flags & L2S_CONV_RELU) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-      }
-      if (p.ref) {
-        const unsigned w[4] = {rv[k].x, rv[k].y, rv[k].z, rv[k].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (!(__uint_as_float(w[e] << 16) > 0.f)) v[2 * e] = 0.f;
-          if (!(__uint_as_float(w[e] & 0xFFFF0000u) > 0.f)) v[2 * e + 1] = 0.f;
-        }
-      }
-      u32x4v pk;
-      pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16); pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-      pk.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16); pk.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
-      const int n = n0 + col;
-      __builtin_amdgcn_raw_buffer_store_b128(pk, ry, off[k] != NOPE ? (unsigned)((off[k] * p.ldy + n) * 2) : NOPE, 0, 0);
-    }
-  }
-}
-
-// the chunk map of igemm_epilogue_lds128 (one pass): thread tid owns chunks tid + NT k of the ROWS x BN tile, 8 channels each
-template <int ROWS, int NT, int BN>
-__device__ __forceinline__ void igemm_epilogue_prefetch(const l2s_conv_desc& p, int m0, int n0, int M, int tid, u32x4v* av, u32x4v* rv) {
-  constexpr int CPR = BN / 8, CH = ROWS * CPR, IT = (CH + NT - 1) / NT;
-  constexpr unsigned NOPE = 0x80000000u;
-  const auto radd = __builtin_amdgcn_make_buffer_rsrc((void*)(p.add ? p.add : p.y), 0, 0x7FFFFFFF, 0x00020000);
-  const auto rref = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ref ? p.ref : p.y), 0, 0x7FFFFFFF, 0x00020000);
-#pragma unroll
-  for (int k = 0; k < IT; ++k) {
-    const int c = tid + NT * k, row = c / CPR, col = (c % CPR) * 8;
-    const int m = m0 + row, n = n0 + col;
-    const bool ok = c < CH && m < M && n < p.Cout;
-    if (p.add) av[k] = __builtin_amdgcn_raw_buffer_load_b128(radd, ok ? (unsigned)((m * p.ldadd + n) * 2) : NOPE, 0, 0);
-    if (p.ref) rv[k] = __builtin_amdgcn_raw_buffer_load_b128(rref, ok ? (unsigned)((m * p.ldref + n) * 2) : NOPE, 0, 0);
+    const bool pre = PASSES == 1 && pre_add && pre_ref;
+    if (!pre) igemm_epilogue_prefetch<RP, NT, BN>(p, m0 + h * RP, n0, M, tid, av, rv);
+    igemm_staged_store<RP, NT, BN>(p, st, m0 + h * RP, n0, M, tid, pre ? pre_add : av, pre ? pre_ref : rv);
   }
 }
 
@@ -286,40 +320,24 @@ __device__ __forceinline__ void igemm_epilogue(const l2s_conv_desc& p, f32x4 (&a
       const bool full = (n + 3 < p.Cout);
       if (full && vec_ok) {
         if (p.bias) { const float4 b4 = *(const float4*)(p.bias + oc); v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w; }
-        if (p.add) {
-          const T* ap = (const T*)p.add + orow2 * p.ldadd + oc;
-          if (sizeof(T) == 4) { const float4 a4 = *(const float4*)ap; v[0] += a4.x; v[1] += a4.y; v[2] += a4.z; v[3] += a4.w; }
-          else { const uint2 a2 = *(const uint2*)ap; v[0] += __uint_as_float(a2.x << 16); v[1] += __uint_as_float(a2.x & 0xFFFF0000u);
-                 v[2] += __uint_as_float(a2.y << 16); v[3] += __uint_as_float(a2.y & 0xFFFF0000u); }
-        }
-        if (p.flags & L2S_CONV_RELU) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-        if (p.ref) {
-          const T* rp = (const T*)p.ref + orow2 * p.ldref + oc;
-          float rv[4];
-          if (sizeof(T) == 4) { const float4 r4 = *(const float4*)rp; rv[0] = r4.x; rv[1] = r4.y; rv[2] = r4.z; rv[3] = r4.w; }
-          else { const uint2 r2 = *(const uint2*)rp; rv[0] = __uint_as_float(r2.x << 16); rv[1] = __uint_as_float(r2.x & 0xFFFF0000u);
-                 rv[2] = __uint_as_float(r2.y << 16); rv[3] = __uint_as_float(r2.y & 0xFFFF0000u); }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (!(rv[r] > 0.f)) v[r] = 0.f;
-        }
+        typedef typename std::conditional<sizeof(T) == 4, u32x4v, u32x2>::type OPV;   // four channels of an operand
+        igemm_finish_from<4, sizeof(T) == 4>(p, v, [&] { return *(const OPV*)((const T*)p.add + orow2 * p.ldadd + oc); },
+                                             [&] { return *(const OPV*)((const T*)p.ref + orow2 * p.ldref + oc); });
         if (OUTF32 || sizeof(T) == 4) {
           *(float4*)((float*)p.y + orow2 * p.ldy + oc) = make_float4(v[0], v[1], v[2], v[3]);
         } else {
-          uint2 pk;
-          pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-          pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-          *(uint2*)((T*)p.y + orow2 * p.ldy + oc) = pk;
+          *(u32x2*)((T*)p.y + orow2 * p.ldy + oc) = igemm_pack_bf<u32x2>(v);
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           if (n + r >= p.Cout) break;
-          if (p.bias) v[r] += p.bias[oc + r];
-          if (p.add) v[r] += Elem<T>::ld((const T*)p.add + orow2 * p.ldadd + oc + r);
-          if (p.flags & L2S_CONV_RELU) v[r] = fmaxf(v[r], 0.f);
-          if (p.ref) { if (!(Elem<T>::ld((const T*)p.ref + orow2 * p.ldref + oc + r) > 0.f)) v[r] = 0.f; }
-          if (OUTF32) ((float*)p.y)[orow2 * p.ldy + oc + r] = v[r];
-          else Elem<T>::st((T*)p.y + orow2 * p.ldy + oc + r, v[r]);
+          float v1[1] = {v[r]};
+          if (p.bias) v1[0] += p.bias[oc + r];
+          igemm_finish_from<1, true>(p, v1, [&] { return Elem<T>::ld((const T*)p.add + orow2 * p.ldadd + oc + r); },
+                                     [&] { return Elem<T>::ld((const T*)p.ref + orow2 * p.ldref + oc + r); });
+          if (OUTF32) ((float*)p.y)[orow2 * p.ldy + oc + r] = v1[0];
+          else Elem<T>::st((T*)p.y + orow2 * p.ldy + oc + r, v1[0]);
         }
       }
     }
@@ -357,17 +375,8 @@ __global__ __launch_bounds__(256) void igemm_kernel(const l2s_conv_desc p) {
   const int wm = wave >> 1, wn = wave & 1;
   const int M = p.n_img * p.OH * p.OW;
   const int K = p.KH * p.KW * p.Cin;
-  // XCD-aware tile order (1-D grid): consecutive workgroup ids are dealt round-robin over the 8 XCDs, so id % 8 labels
-  // the XCD.  The tile list is cut into 8 contiguous chunks, one per XCD, ordered so that a chunk's operands fit the
-  // XCD's 4 MiB L2 (xcd_mode 0: M-chunks, n fastest -> A tile reused across its n-tiles, all of W resident;
-  // xcd_mode 1: N-chunks, m fastest -> one W column block resident, A streamed).  Speed only, never correctness.
   int mt, nt;
-  {
-    const int MT = (M + BM - 1) / BM, NT = (p.Cout + BN - 1) / BN, G = MT * NT;
-    const int L = blockIdx.x, x = L & 7, slot = L >> 3, q = G >> 3, r = G & 7;
-    const int t = x * q + min(x, r) + slot;
-    if (p.xcd_mode == 0) { mt = t / NT; nt = t - mt * NT; } else { nt = t / MT; mt = t - nt * MT; }
-  }
+  igemm_tile_of(blockIdx.x, (M + BM - 1) / BM, (p.Cout + BN - 1) / BN, p.xcd_mode, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   const T* __restrict__ X = (const T*)p.x;
   const T* __restrict__ Wt = (const T*)p.w;
@@ -521,12 +530,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (BM * BN >= 128 * 128 && WGM * WGN 
   const int M = p.n_img * p.OH * p.OW;
   const int K = p.KH * p.KW * p.Cin;
   int mt, nt;
-  {
-    const int MT = (M + BM - 1) / BM, NT = (p.Cout + BN - 1) / BN, G = MT * NT;
-    const int L = blockIdx.x, x = L & 7, slot = L >> 3, q = G >> 3, r = G & 7;
-    const int t = x * q + min(x, r) + slot;
-    if (p.xcd_mode == 0) { mt = t / NT; nt = t - mt * NT; } else { nt = t / MT; mt = t - nt * MT; }
-  }
+  igemm_tile_of(blockIdx.x, (M + BM - 1) / BM, (p.Cout + BN - 1) / BN, p.xcd_mode, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   char* smem = smem_all;
   const long xpix = (long)p.n_img * p.IH * p.IW;
@@ -690,10 +694,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (BM * BN >= 128 * 128 && WGM * WGN 
   }
   if constexpr (sizeof(T) == 2 && !OUTF32 && ((BM == 128 && BN == 128) || (BM == 128 && BN == 64) || (BM == 64 && BN == 64)) && WGM == 2 && WGN == 2) {
     // whole-row 16-byte accesses through an LDS-staged fp32 tile when every row pitch allows it
-    const bool plain = !(p.flags & (L2S_CONV_DECONV2X2 | L2S_CONV_SCATTER)) && !(p.ldy & 7) && !(p.ldadd & 7) && !(p.ldref & 7) && !(p.Cout & 7) &&
-                       !((uintptr_t)p.y & 15) && !((uintptr_t)p.add & 15) && !((uintptr_t)p.ref & 15) && !((uintptr_t)p.bias & 15) &&
-                       (long)M * p.ldy * 2 < (1L << 31) && (!p.add || (long)M * p.ldadd * 2 < (1L << 31)) && (!p.ref || (long)M * p.ldref * 2 < (1L << 31));
-    if (plain) { igemm_epilogue_lds128<TM, TN, WM, WN, WGM, NTG, BN, (BM == 128 ? 2 : 1)>(p, acc, m0, n0, wm, wn, fr, fg, M, smem_all); return; }
+    if (igemm_plain(p, M)) { igemm_epilogue_lds128<TM, TN, WM, WN, WGM, NTG, BN, (BM == 128 ? 2 : 1)>(p, acc, m0, n0, wm, wn, fr, fg, M, smem_all); return; }
   }
   igemm_epilogue<T, TM, TN, WM, WN, OUTF32>(p, acc, m0, n0, wm, wn, fr, fg, M);
 }
@@ -724,12 +725,7 @@ __global__ __launch_bounds__(512, 2) void igemm_ws64_kernel(const l2s_conv_desc 
   const int M = p.n_img * p.OH * p.OW;
   const int K = p.KH * p.KW * p.Cin;
   int mt, nt;
-  {
-    const int MT = (M + BM - 1) / BM, NT = (p.Cout + BN - 1) / BN, G = MT * NT;
-    const int L = blockIdx.x, x = L & 7, slot = L >> 3, q = G >> 3, r = G & 7;
-    const int t = x * q + min(x, r) + slot;
-    if (p.xcd_mode == 0) { mt = t / NT; nt = t - mt * NT; } else { nt = t / MT; mt = t - nt * MT; }
-  }
+  igemm_tile_of(blockIdx.x, (M + BM - 1) / BM, (p.Cout + BN - 1) / BN, p.xcd_mode, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   // split-K (gridDim.z > 1): this workgroup multiplies slices [kt0, kt0 + KT) and leaves its partial tile in slab blockIdx.z
   int kt0 = 0, KT = K / BK;
@@ -832,10 +828,7 @@ __global__ __launch_bounds__(512, 2) void igemm_ws64_kernel(const l2s_conv_desc 
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = wave_all;
   const int wm = wave >> 1, wn = wave & 1;
   const int fr = lane & 15, fg = lane >> 4;
-  const bool plain = !(p.flags & (L2S_CONV_DECONV2X2 | L2S_CONV_SCATTER)) && !(p.ldy & 7) && !(p.ldadd & 7) && !(p.ldref & 7) && !(p.Cout & 7) &&
-                     !((uintptr_t)p.y & 15) && !((uintptr_t)p.add & 15) && !((uintptr_t)p.ref & 15) && !((uintptr_t)p.bias & 15) &&
-                     (long)M * p.ldy * 2 < (1L << 31) && (!p.add || (long)M * p.ldadd * 2 < (1L << 31)) && (!p.ref || (long)M * p.ldref * 2 < (1L << 31));
-  const bool staged = plain && gridDim.z == 1;
+  const bool staged = igemm_plain(p, M) && gridDim.z == 1;
   // residual / ReLU-mask operands of the LDS-staged epilogue, requested before the K loop (these waves issue no other global load)
   constexpr int EIT = (BM * (BN / 8) + 255) / 256;
   u32x4v eav[EIT], erv[EIT];
@@ -934,12 +927,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm_sp_kernel(const l2s_conv
   const int M = p.n_img * p.OH * p.OW;
   const int K = p.KH * p.KW * p.Cin;
   int mt, nt;
-  {
-    const int MT = (M + BM - 1) / BM, NT = (p.Cout + BN - 1) / BN, G = MT * NT;
-    const int L = blockIdx.x, x = L & 7, slot = L >> 3, q = G >> 3, r = G & 7;
-    const int t = x * q + min(x, r) + slot;
-    if (p.xcd_mode == 0) { mt = t / NT; nt = t - mt * NT; } else { nt = t / MT; mt = t - nt * MT; }
-  }
+  igemm_tile_of(blockIdx.x, (M + BM - 1) / BM, (p.Cout + BN - 1) / BN, p.xcd_mode, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   const long xpix = (long)p.n_img * p.IH * p.IW;
   const auto rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)(((xpix - 1) * p.ldx + p.Cin) * (long)sizeof(T)), 0x00020000);
@@ -1106,10 +1094,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm_sp_kernel(const l2s_conv
     }
   }
   if constexpr (sizeof(T) == 2 && !OUTF32 && BN == 128) {
-    const bool plain = !(p.flags & (L2S_CONV_DECONV2X2 | L2S_CONV_SCATTER)) && !(p.ldy & 7) && !(p.ldadd & 7) && !(p.ldref & 7) && !(p.Cout & 7) &&
-                       !((uintptr_t)p.y & 15) && !((uintptr_t)p.add & 15) && !((uintptr_t)p.ref & 15) && !((uintptr_t)p.bias & 15) &&
-                       (long)M * p.ldy * 2 < (1L << 31) && (!p.add || (long)M * p.ldadd * 2 < (1L << 31)) && (!p.ref || (long)M * p.ldref * 2 < (1L << 31));
-    if (plain) { igemm_epilogue_lds128<TM, TN, WM, WN, WGM, NTG, BN, 1>(p, acc, m0, n0, wm, wn, fr, fg, M, smem); return; }
+    if (igemm_plain(p, M)) { igemm_epilogue_lds128<TM, TN, WM, WN, WGM, NTG, BN, 1>(p, acc, m0, n0, wm, wn, fr, fg, M, smem); return; }
   }
   igemm_epilogue<T, TM, TN, WM, WN, OUTF32>(p, acc, m0, n0, wm, wn, fr, fg, M);
 }
@@ -1157,12 +1142,7 @@ __global__ __launch_bounds__(512) void igemm_dma_kernel(const l2s_conv_desc p) {
   const int M = p.n_img * p.OH * p.OW;
   const int K = p.KH * p.KW * p.Cin;
   int mt, nt;
-  {
-    const int MT = (M + BM - 1) / BM, NT = (p.Cout + BN - 1) / BN, G = MT * NT;
-    const int L = blockIdx.x, x = L & 7, slot = L >> 3, q = G >> 3, r = G & 7;
-    const int t = x * q + min(x, r) + slot;
-    if (p.xcd_mode == 0) { mt = t / NT; nt = t - mt * NT; } else { nt = t / MT; mt = t - nt * MT; }
-  }
+  igemm_tile_of(blockIdx.x, (M + BM - 1) / BM, (p.Cout + BN - 1) / BN, p.xcd_mode, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   const long xpix = (long)p.n_img * p.IH * p.IW;
@@ -1340,12 +1320,7 @@ __global__ __launch_bounds__(512) void igemm_dma_kernel(const l2s_conv_desc p) {
     if (blockIdx.x == 0 && tid < 2 * 24 * 8 + 2 * 24 + 4 && p.ws) ((unsigned long long*)p.ws)[tid] = ((unsigned long long*)(smem + 3 * STG))[tid];
     __syncthreads();
   }
-  {
-    const bool plain = !(p.flags & (L2S_CONV_DECONV2X2 | L2S_CONV_SCATTER)) && !(p.ldy & 7) && !(p.ldadd & 7) && !(p.ldref & 7) && !(p.Cout & 7) &&
-                       !((uintptr_t)p.y & 15) && !((uintptr_t)p.add & 15) && !((uintptr_t)p.ref & 15) && !((uintptr_t)p.bias & 15) &&
-                       (long)M * p.ldy * 2 < (1L << 31) && (!p.add || (long)M * p.ldadd * 2 < (1L << 31)) && (!p.ref || (long)M * p.ldref * 2 < (1L << 31));
-    if (plain) { igemm_epilogue_lds128<TM, TN, WM, WN, WGM, 512, BN, 1>(p, acc, m0, n0, wm, wn, fr, fg, M, smem); return; }
-  }
+  if (igemm_plain(p, M)) { igemm_epilogue_lds128<TM, TN, WM, WN, WGM, 512, BN, 1>(p, acc, m0, n0, wm, wn, fr, fg, M, smem); return; }
   igemm_epilogue<T, TM, TN, WM, WN, false>(p, acc, m0, n0, wm, wn, fr, fg, M);
 }
 
@@ -1374,12 +1349,7 @@ __device__ __forceinline__ void igemm_dma196_body(const l2s_conv_desc& p, char* 
   const int M = p.n_img * p.OH * p.OW;
   const int K = p.KH * p.KW * p.Cin;
   int mt, nt;
-  {
-    const int MT = (M + T196 - 1) / T196, NT = (p.Cout + BN - 1) / BN, G = MT * NT;
-    const int L = blockIdx.x, x = L & 7, slot = L >> 3, q = G >> 3, r = G & 7;
-    const int t = x * q + min(x, r) + slot;
-    if (p.xcd_mode == 0) { mt = t / NT; nt = t - mt * NT; } else { nt = t / MT; mt = t - nt * MT; }
-  }
+  igemm_tile_of(blockIdx.x, (M + T196 - 1) / T196, (p.Cout + BN - 1) / BN, p.xcd_mode, mt, nt);
   const int m0 = mt * T196, n0 = nt * BN;
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   const long xpix = (long)p.n_img * p.IH * p.IW;
@@ -1506,15 +1476,11 @@ __device__ __forceinline__ void igemm_dma196_body(const l2s_conv_desc& p, char* 
     st = st == 2 ? 0 : st + 1;
   }
   if (grp == 0) wg_barrier();
-  // ---- epilogue: the fp32 tile (+ bias) through LDS (row pitch BN + 4 floats), then bias / residual / ReLU / mask in fp32, one rounding,
-  // 16-byte stores of whole rows (the arithmetic of igemm_epilogue_lds128); rows >= 196 of the tile are the next tile's ----
+  // ---- epilogue: the fp32 tile (+ bias) through LDS, then the staged store of igemm_epilogue_lds128 limited to the tile's first 196 rows
+  // (rows >= 196 are the next tile's) ----
   {
-    constexpr int LDW = BN + 4, CPR = BN / 8, CH = R208 * CPR, NTH = 512, IT = (CH + NTH - 1) / NTH;
-    constexpr unsigned NOPE = 0x80000000u;
+    constexpr int LDW = BN + 4, NTH = 512;
     float* stg = (float*)smem;
-    const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, 0x7FFFFFFF, 0x00020000);
-    const auto radd = __builtin_amdgcn_make_buffer_rsrc((void*)(p.add ? p.add : p.y), 0, 0x7FFFFFFF, 0x00020000);
-    const auto rref = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ref ? p.ref : p.y), 0, 0x7FFFFFFF, 0x00020000);
     f32x4 bv[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -1532,45 +1498,9 @@ __device__ __forceinline__ void igemm_dma196_body(const l2s_conv_desc& p, char* 
         *(f32x4*)(stg + (rbase + i * 16 + fr) * LDW + wn * 64 + j * 16 + fg * 4) = v;
       }
     __syncthreads();
-    u32x4v av[IT], rv[IT];
-    unsigned off[IT];
-#pragma unroll
-    for (int k = 0; k < IT; ++k) {
-      const int c = tid + NTH * k, row = c / CPR, col = (c % CPR) * 8;
-      const int m = m0 + row, n = n0 + col;
-      const bool ok = c < CH && row < T196 && m < M && n < p.Cout;
-      off[k] = ok ? (unsigned)m : NOPE;
-      if (p.add) av[k] = __builtin_amdgcn_raw_buffer_load_b128(radd, ok ? (unsigned)((m * p.ldadd + n) * 2) : NOPE, 0, 0);
-      if (p.ref) rv[k] = __builtin_amdgcn_raw_buffer_load_b128(rref, ok ? (unsigned)((m * p.ldref + n) * 2) : NOPE, 0, 0);
-    }
-#pragma unroll
-    for (int k = 0; k < IT; ++k) {
-      const int c = min(tid + NTH * k, CH - 1), row = c / CPR, col = (c % CPR) * 8;
-      const f32x4 lo = *(const f32x4*)(stg + row * LDW + col), hi = *(const f32x4*)(stg + row * LDW + col + 4);
-      float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      if (p.add) {
-        const unsigned w[4] = {av[k].x, av[k].y, av[k].z, av[k].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { v[2 * e] += __uint_as_float(w[e] << 16); v[2 * e + 1] += __uint_as_float(w[e] & 0xFFFF0000u); }
-      }
-      if (p.flags & L2S_CONV_RELU) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-      }
-      if (p.ref) {
-        const unsigned w[4] = {rv[k].x, rv[k].y, rv[k].z, rv[k].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (!(__uint_as_float(w[e] << 16) > 0.f)) v[2 * e] = 0.f;
-          if (!(__uint_as_float(w[e] & 0xFFFF0000u) > 0.f)) v[2 * e + 1] = 0.f;
-        }
-      }
-      u32x4v pk;
-      pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16); pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-      pk.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16); pk.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
-      const int n = n0 + col;
-      __builtin_amdgcn_raw_buffer_store_b128(pk, ry, off[k] != NOPE ? (unsigned)((off[k] * p.ldy + n) * 2) : NOPE, 0, 0);
-    }
+    u32x4v av[EpiChunks<R208, NTH, BN>::IT], rv[EpiChunks<R208, NTH, BN>::IT];
+    igemm_epilogue_prefetch<R208, NTH, BN, T196>(p, m0, n0, M, tid, av, rv);
+    igemm_staged_store<R208, NTH, BN, T196>(p, stg, m0, n0, M, tid, av, rv);
   }
 }
 __global__ __launch_bounds__(512) void igemm_dma196_kernel(const l2s_conv_desc p) {
@@ -1581,8 +1511,8 @@ __global__ __launch_bounds__(512) void igemm_dma196_kernel(const l2s_conv_desc p
   else igemm_dma196_body<3>(p, smem, wave, lane);
 }
 
-// ---- per-WAVE epilogue of a 64 x 64 sub-tile (bf16 out, plain row-major output): the arithmetic of igemm_epilogue_fast (bias, residual,
-// ReLU, mask in fp32, one rounding; operands requested up front in the MFMA layout), but the results leave through 2 KiB of LDS that
+// ---- per-WAVE epilogue of a 64 x 64 sub-tile (bf16 out, plain row-major output): operands requested up front in the MFMA layout as in
+// igemm_epilogue_fast, but the results leave through 2 KiB of LDS that
 // belong to this wave alone: 16 rows x 64 channels at a time are written in the MFMA layout (8 bytes per lane) and read back row-major
 // (16 bytes per lane), so the stores cover whole 128-byte runs instead of 32-byte ones (the persistent tile with direct stores:
 // 80 us for the 100 MB of output + residual of the N = 2048 launches).  No barrier: LDS operations of one wave are ordered.
@@ -1591,12 +1521,10 @@ __global__ __launch_bounds__(512) void igemm_dma196_kernel(const l2s_conv_desc p
 // tile's last MUL slot instead of 64 (with both arrays the kernel spilled)
 template <int TM, int TN, int WM, int WN>
 __device__ __forceinline__ void igemm_epilogue_wave_prefetch(const l2s_conv_desc& p, int m0, int n0, int wm, int wn, int lane, int M, f32x4 (&bv)[TN], u32x2 (&ov)[TM][TN]) {
-  constexpr unsigned NOPE = 0x80000000u;
   const int fr = lane & 15, fg = lane >> 4;
   const void* op = p.add ? p.add : p.ref;
   const int ldo = p.add ? p.ldadd : p.ldref;
-  const auto rop = __builtin_amdgcn_make_buffer_rsrc((void*)(op ? op : p.y), 0, 0x7FFFFFFF, 0x00020000);
-  const auto rbias = __builtin_amdgcn_make_buffer_rsrc((void*)(p.bias ? (const void*)p.bias : (const void*)p.y), 0, 0x7FFFFFFF, 0x00020000);
+  const auto rop = whole_rsrc(op, p.y), rbias = whole_rsrc(p.bias, p.y);
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int n = n0 + wn * WN + j * 16 + fg * 4;
@@ -1616,9 +1544,8 @@ template <int TM, int TN, int WM, int WN>
 __device__ __forceinline__ void igemm_epilogue_wave(const l2s_conv_desc& p, f32x4 (&acc)[TM][TN], int m0, int n0, int wm, int wn, int lane, int M, char* wlds,
                                                     const f32x4 (&bv)[TN], const u32x2 (&ov)[TM][TN]) {
   static_assert(TN == 4 && WN == 64, "64-channel sub-tiles");
-  constexpr unsigned NOPE = 0x80000000u;
   const int fr = lane & 15, fg = lane >> 4;
-  const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, 0x7FFFFFFF, 0x00020000);
+  const auto ry = whole_rsrc(p.y);
   // staging addresses: write (row fr, 8 bytes of chunk 2 j + (fg >> 1)); read (row lane >> 3 (+ 8), chunk lane & 7)
   const int wsw = (fr >> 1) & 7;
   const int rrow = lane >> 3, rch = lane & 7;
@@ -1627,17 +1554,8 @@ __device__ __forceinline__ void igemm_epilogue_wave(const l2s_conv_desc& p, f32x
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       float v[4] = {acc[i][j][0] + bv[j][0], acc[i][j][1] + bv[j][1], acc[i][j][2] + bv[j][2], acc[i][j][3] + bv[j][3]};   // (no bias: zeros were loaded)
-      const float o[4] = {__uint_as_float(ov[i][j].x << 16), __uint_as_float(ov[i][j].x & 0xFFFF0000u), __uint_as_float(ov[i][j].y << 16), __uint_as_float(ov[i][j].y & 0xFFFF0000u)};
-      if (p.add) { v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3]; }
-      if (p.flags & L2S_CONV_RELU) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-      if (p.ref) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) if (!(o[e] > 0.f)) v[e] = 0.f;
-      }
-      u32x2 pk;
-      pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-      pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-      *(u32x2*)(wlds + fr * 128 + (((2 * j + (fg >> 1)) ^ wsw) << 4) + ((fg & 1) << 3)) = pk;
+      igemm_finish<4, false>(p, v, ov[i][j], ov[i][j]);             // (the one operand register is the residual or the mask)
+      *(u32x2*)(wlds + fr * 128 + (((2 * j + (fg >> 1)) ^ wsw) << 4) + ((fg & 1) << 3)) = igemm_pack_bf<u32x2>(v);
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -1665,14 +1583,11 @@ __device__ __forceinline__ void igemm_epilogue_wave(const l2s_conv_desc& p, f32x
 template <int TM, int TN, bool BOTH>
 __device__ __forceinline__ void igemm_epilogue_wave128(const l2s_conv_desc& p, f32x4 (&acc)[TM][TN], int m0, int n0, int wm, int wn, int lane, int M, char* wlds) {
   static_assert(TN == 8, "128-channel sub-tiles");
-  constexpr unsigned NOPE = 0x80000000u;
   constexpr int WM = TM * 16, WN = TN * 16;
   const int fr = lane & 15, fg = lane >> 4;
   const void* op = p.add ? p.add : p.ref;
   const int ldo = p.add ? p.ldadd : p.ldref;
-  const auto rop = __builtin_amdgcn_make_buffer_rsrc((void*)(op ? op : p.y), 0, 0x7FFFFFFF, 0x00020000);
-  const auto rbias = __builtin_amdgcn_make_buffer_rsrc((void*)(p.bias ? (const void*)p.bias : (const void*)p.y), 0, 0x7FFFFFFF, 0x00020000);
-  const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, 0x7FFFFFFF, 0x00020000);
+  const auto rop = whole_rsrc(op, p.y), rbias = whole_rsrc(p.bias, p.y), ry = whole_rsrc(p.y);
   f32x4 bv[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
@@ -1680,7 +1595,7 @@ __device__ __forceinline__ void igemm_epilogue_wave128(const l2s_conv_desc& p, f
     bv[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rbias, (p.bias && n < p.Cout) ? (unsigned)(n * 4) : NOPE, 0, 0));
   }
   // BOTH: residual AND mask (the data gradient of a block's first 1x1: dx = mask(conv^T(dz) + g)): `op` is the residual, `rv` the mask operand
-  const auto rref = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ref ? p.ref : p.y), 0, 0x7FFFFFFF, 0x00020000);
+  const auto rref = whole_rsrc(p.ref, p.y);
   u32x2 ov[2][TN], rv[BOTH ? 2 : 1][BOTH ? TN : 1];       // operands of row block i, requested one block ahead
   auto fetch = [&](int i, u32x2 (&o)[TN]) {
     const int m = m0 + wm * WM + i * 16 + fr;
@@ -1700,22 +1615,9 @@ __device__ __forceinline__ void igemm_epilogue_wave128(const l2s_conv_desc& p, f
     for (int j = 0; j < TN; ++j) {
       const u32x2 oo = ov[i & 1][j];
       float v[4] = {acc[i][j][0] + bv[j][0], acc[i][j][1] + bv[j][1], acc[i][j][2] + bv[j][2], acc[i][j][3] + bv[j][3]};   // (no bias: zeros were loaded)
-      const float o[4] = {__uint_as_float(oo.x << 16), __uint_as_float(oo.x & 0xFFFF0000u), __uint_as_float(oo.y << 16), __uint_as_float(oo.y & 0xFFFF0000u)};
-      if (p.add) { v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3]; }
-      if (p.flags & L2S_CONV_RELU) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-      if (p.ref) {
-        float q[4] = {o[0], o[1], o[2], o[3]};
-        if constexpr (BOTH) {
-          const u32x2 rr = rv[i & 1][j];
-          q[0] = __uint_as_float(rr.x << 16); q[1] = __uint_as_float(rr.x & 0xFFFF0000u); q[2] = __uint_as_float(rr.y << 16); q[3] = __uint_as_float(rr.y & 0xFFFF0000u);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) if (!(q[e] > 0.f)) v[e] = 0.f;
-      }
-      u32x2 pk;
-      pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-      pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-      *(u32x2*)(wlds + fr * 256 + (((2 * j + (fg >> 1)) ^ fr) << 4) + ((fg & 1) << 3)) = pk;
+      if constexpr (BOTH) igemm_finish<4, false>(p, v, oo, rv[i & 1][j]);
+      else igemm_finish<4, false>(p, v, oo, oo);                    // (the one operand register is the residual or the mask)
+      *(u32x2*)(wlds + fr * 256 + (((2 * j + (fg >> 1)) ^ fr) << 4) + ((fg & 1) << 3)) = igemm_pack_bf<u32x2>(v);
     }
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
@@ -1742,12 +1644,7 @@ __global__ __launch_bounds__(512) void igemm_dma256_kernel(const l2s_conv_desc p
   const int M = p.n_img * p.OH * p.OW;
   const int K = p.Cin;                                     // 1x1
   int mt, nt;
-  {
-    const int MT = (M + BM - 1) / BM, NT = (p.Cout + BN - 1) / BN, G = MT * NT;
-    const int L = blockIdx.x, x = L & 7, slot = L >> 3, q = G >> 3, r = G & 7;
-    const int t = x * q + min(x, r) + slot;
-    if (p.xcd_mode == 0) { mt = t / NT; nt = t - mt * NT; } else { nt = t / MT; mt = t - nt * MT; }
-  }
+  igemm_tile_of(blockIdx.x, (M + BM - 1) / BM, (p.Cout + BN - 1) / BN, p.xcd_mode, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   i32x4s rx, rw;
@@ -1853,10 +1750,8 @@ __global__ __launch_bounds__(512) void igemm_pdma_kernel(const l2s_conv_desc p) 
   // this workgroup's tiles: L = blockIdx.x, + gridDim.x, ... in the XCD-aware order of the one-shot kernel (gridDim.x is a multiple of 8)
   const int ntl = (G - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
   auto tile_of = [&](int i, int& m0_, int& n0_) {
-    const int Lx = blockIdx.x + i * gridDim.x, x = Lx & 7, slot = Lx >> 3, q = G >> 3, r = G & 7;
-    const int t = x * q + min(x, r) + slot;
     int mt, nt;
-    if (p.xcd_mode == 0) { mt = t / NT; nt = t - mt * NT; } else { nt = t / MT; mt = t - nt * MT; }
+    igemm_tile_of(blockIdx.x + i * gridDim.x, MT, NT, p.xcd_mode, mt, nt);
     m0_ = mt * BM; n0_ = nt * BN;
   };
   if (ntl <= 0) return;
@@ -2010,19 +1905,13 @@ __global__ __launch_bounds__(512) void igemm_ks64_kernel(const l2s_conv_desc p) 
   if (p.prio) __builtin_amdgcn_s_setprio(3);
   typedef bf16_t T;
   constexpr int BM = 64, BN = 64, RB2 = 256, BK = 128, STG = (BM + BN) * RB2, PW = 4;   // PW: pieces per requester wave and operand
-  constexpr unsigned NOPE = 0x80000000u;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int M = p.n_img * p.OH * p.OW;
   const int K = p.KH * p.KW * p.Cin;
   int mt, nt;
-  {
-    const int MT = (M + BM - 1) / BM, NT = (p.Cout + BN - 1) / BN, G = MT * NT;
-    const int L = blockIdx.x, x = L & 7, slot = L >> 3, q = G >> 3, r = G & 7;
-    const int t = x * q + min(x, r) + slot;
-    if (p.xcd_mode == 0) { mt = t / NT; nt = t - mt * NT; } else { nt = t / MT; mt = t - nt * MT; }
-  }
+  igemm_tile_of(blockIdx.x, (M + BM - 1) / BM, (p.Cout + BN - 1) / BN, p.xcd_mode, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   const int KT = K / BK;
 
@@ -2099,27 +1988,13 @@ __global__ __launch_bounds__(512) void igemm_ks64_kernel(const l2s_conv_desc p) 
 
   // ---------------- multipliers: wave w = K quarter w of every slice ----------------
   const int fr = lane & 15, fg = lane >> 4;
-  const bool plain = !(p.flags & (L2S_CONV_DECONV2X2 | L2S_CONV_SCATTER)) && !(p.ldy & 7) && !(p.ldadd & 7) && !(p.ldref & 7) && !(p.Cout & 7) &&
-                     !((uintptr_t)p.y & 15) && !((uintptr_t)p.add & 15) && !((uintptr_t)p.ref & 15) && !((uintptr_t)p.bias & 15) &&
-                     (long)M * p.ldy * 2 < (1L << 31) && (!p.add || (long)M * p.ldadd * 2 < (1L << 31)) && (!p.ref || (long)M * p.ldref * 2 < (1L << 31));
-  // epilogue operands of this thread's two output chunks (row = chunk / 8, 8 channels each), requested now: their latency passes under the K loop
-  const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, 0x7FFFFFFF, 0x00020000);
-  const auto radd = __builtin_amdgcn_make_buffer_rsrc((void*)(p.add ? p.add : p.y), 0, 0x7FFFFFFF, 0x00020000);
-  const auto rref = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ref ? p.ref : p.y), 0, 0x7FFFFFFF, 0x00020000);
-  u32x4v av[2], rv[2]; unsigned orow[2];
+  const bool plain = igemm_plain(p, M);
+  // epilogue operands of this thread's two output chunks (the map of the staged epilogues), requested now: their latency passes under the K loop
+  typedef EpiChunks<BM, 256, BN> EC;
+  u32x4v av[EC::IT], rv[EC::IT];
   f32x4 bq[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};   // bias of the thread's 8 columns (both chunks: same columns)
   if (plain && p.bias && n0 + (tid & 7) * 8 < p.Cout) { bq[0] = *(const f32x4*)(p.bias + n0 + (tid & 7) * 8); bq[1] = *(const f32x4*)(p.bias + n0 + (tid & 7) * 8 + 4); }
-  if (plain) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int c = tid + 256 * k, row = c >> 3, col = (c & 7) * 8;
-      const int m = m0 + row, n = n0 + col;
-      const bool ok = m < M && n < p.Cout;
-      orow[k] = ok ? (unsigned)m : NOPE;
-      if (p.add) av[k] = __builtin_amdgcn_raw_buffer_load_b128(radd, ok ? (unsigned)((m * p.ldadd + n) * 2) : NOPE, 0, 0);
-      if (p.ref) rv[k] = __builtin_amdgcn_raw_buffer_load_b128(rref, ok ? (unsigned)((m * p.ldref + n) * 2) : NOPE, 0, 0);
-    }
-  }
+  if (plain) igemm_epilogue_prefetch<BM, 256, BN>(p, m0, n0, M, tid, av, rv);
   f32x4 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -2152,9 +2027,12 @@ __global__ __launch_bounds__(512) void igemm_ks64_kernel(const l2s_conv_desc p) 
     for (int j = 0; j < 4; ++j) *(f32x4*)(part + (wave * BM + i * 16 + fr) * LDW + j * 16 + fg * 4) = acc[i][j];
   __syncthreads();
   if (plain) {
+    const auto ry = whole_rsrc(p.y);
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int c = tid + 256 * k, row = c >> 3, col = (c & 7) * 8;
+    for (int k = 0; k < EC::IT; ++k) {
+      int m, n;
+      const bool ok = EC::at(p, m0, n0, M, tid, k, m, n);
+      const int row = m - m0, col = n - n0;
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = 0.f;
@@ -2163,29 +2041,9 @@ __global__ __launch_bounds__(512) void igemm_ks64_kernel(const l2s_conv_desc p) 
         const f32x4 lo = *(const f32x4*)(part + (q * BM + row) * LDW + col), hi = *(const f32x4*)(part + (q * BM + row) * LDW + col + 4);
         v[0] += lo[0]; v[1] += lo[1]; v[2] += lo[2]; v[3] += lo[3]; v[4] += hi[0]; v[5] += hi[1]; v[6] += hi[2]; v[7] += hi[3];
       }
-      const int n = n0 + col;
       if (p.bias) { v[0] += bq[0][0]; v[1] += bq[0][1]; v[2] += bq[0][2]; v[3] += bq[0][3]; v[4] += bq[1][0]; v[5] += bq[1][1]; v[6] += bq[1][2]; v[7] += bq[1][3]; }
-      if (p.add) {
-        const unsigned wv[4] = {av[k].x, av[k].y, av[k].z, av[k].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { v[2 * e] += __uint_as_float(wv[e] << 16); v[2 * e + 1] += __uint_as_float(wv[e] & 0xFFFF0000u); }
-      }
-      if (p.flags & L2S_CONV_RELU) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-      }
-      if (p.ref) {
-        const unsigned wv[4] = {rv[k].x, rv[k].y, rv[k].z, rv[k].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (!(__uint_as_float(wv[e] << 16) > 0.f)) v[2 * e] = 0.f;
-          if (!(__uint_as_float(wv[e] & 0xFFFF0000u) > 0.f)) v[2 * e + 1] = 0.f;
-        }
-      }
-      u32x4v pk;
-      pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16); pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-      pk.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16); pk.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
-      __builtin_amdgcn_raw_buffer_store_b128(pk, ry, orow[k] != NOPE ? (unsigned)((orow[k] * p.ldy + n) * 2) : NOPE, 0, 0);
+      igemm_finish<8, false>(p, v, av[k], rv[k]);
+      __builtin_amdgcn_raw_buffer_store_b128(igemm_pack_bf<u32x4v>(v), ry, ok ? (unsigned)((m * p.ldy + n) * 2) : NOPE, 0, 0);
     }
     return;
   }
@@ -2237,13 +2095,8 @@ __global__ __launch_bounds__(512) void igemm_p3_kernel(const l2s_conv_desc p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int W = p.OW, M = p.OH * p.OW;
   const int K = 9 * p.Cin;
-  int mt, nt;
-  {
-    const int MT = (M + BM - 1) / BM, NT = (p.Cout + BN - 1) / BN, G = MT * NT;
-    const int L = blockIdx.x, x = L & 7, slot = L >> 3, q = G >> 3, r = G & 7;
-    const int t = x * q + min(x, r) + slot;                      // an XCD's chunk of tiles: a few pixel tiles x every channel tile (shared patch in L2)
-    mt = t / NT; nt = t - mt * NT;
-  }
+  int mt, nt;                                                    // mode 0, an XCD's chunk of tiles: a few pixel tiles x every channel tile (shared patch in L2)
+  igemm_tile_of(blockIdx.x, (M + BM - 1) / BM, (p.Cout + BN - 1) / BN, 0, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   const int KT = p.Cin / 32;
 
@@ -2477,9 +2330,7 @@ __global__ __launch_bounds__(512) void roialign_block0_kernel(const l2s_roi_bloc
         float v0 = acc[i][0] + bv[0], v1 = acc[i][1] + bv[1], v2 = acc[i][2] + bv[2], v3 = acc[i][3] + bv[3];
         if (first) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
         if (row < PP && !((p.debug & 4) && nt > 0)) {
-          uint2 pk;
-          pk.x = (uint32_t)f2bf(v0) | ((uint32_t)f2bf(v1) << 16); pk.y = (uint32_t)f2bf(v2) | ((uint32_t)f2bf(v3) << 16);
-          *(uint2*)(y + (long)row * ldy) = pk;
+          *(uint2*)(y + (long)row * ldy) = make_uint2(pack_bf2(v0, v1), pack_bf2(v2, v3));
         }
         acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
       }
@@ -2510,10 +2361,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const l2s_conv_desc 
   float v[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    if (p.bias) v[r] += p.bias[n + r];
-    if (p.add) v[r] += Elem<T>::ld((const T*)p.add + m * p.ldadd + n + r);
-    if (p.flags & L2S_CONV_RELU) v[r] = fmaxf(v[r], 0.f);
-    if (p.ref) { if (!(Elem<T>::ld((const T*)p.ref + m * p.ldref + n + r) > 0.f)) v[r] = 0.f; }
+    float v1[1] = {v[r]};
+    if (p.bias) v1[0] += p.bias[n + r];
+    igemm_finish_from<1, true>(p, v1, [&] { return Elem<T>::ld((const T*)p.add + m * p.ldadd + n + r); },
+                               [&] { return Elem<T>::ld((const T*)p.ref + m * p.ldref + n + r); });
+    v[r] = v1[0];
   }
   if (OUTF32) { float* o = (float*)p.y + m * p.ldy + n; for (int r = 0; r < 4; ++r) o[r] = v[r]; }
   else { T* o = (T*)p.y + m * p.ldy + n; for (int r = 0; r < 4; ++r) Elem<T>::st(o + r, v[r]); }
@@ -2531,8 +2383,7 @@ int launch_splitk_reduce(const l2s_conv_desc& d, int split, hipStream_t st) {
 // second launch costs more than the split saves on every shape tried - 80 tiles x 32 slices 10.9 -> 13.1 us, 80 x 72 (3x3) 14.8 -> 16.7,
 // 120 x 16 7.4 -> 11.0 - and inside the step it made 600x800 images 7 % slower (91 extra launches on layer3's chain) before the profile
 // showed it.  split_k = 0 therefore means "no split".
-static int splitk_factor(const l2s_conv_desc& d, int KT, long tiles64, bool auto_ok) {
-  (void)tiles64; (void)auto_ok;
+static int splitk_factor(const l2s_conv_desc& d, int KT) {
   if (!d.ws || d.split_k <= 1 || (d.flags & (L2S_CONV_SCATTER | L2S_CONV_DECONV2X2)) || (d.Cout % 4)) return 1;
   const long out = (long)d.n_img * d.OH * d.OW * d.Cout;
   int s = d.split_k;
@@ -2542,19 +2393,26 @@ static int splitk_factor(const l2s_conv_desc& d, int KT, long tiles64, bool auto
   return s < 1 ? 1 : s;
 }
 
+// One launch: the kernel's dynamic-LDS limit is raised to max_lds once (the static is the enclosing launcher instantiation's), then L2S_LAUNCH.
+// A macro, not a function template that receives the kernel: l2s::last_kernel is the kernel argument of L2S_LAUNCH as it is spelled.
+#define IGEMM_LAUNCH(kern, grid, block, lds, max_lds, st, d)                                                                             \
+  do {                                                                                                                                    \
+    static bool attr_done = false;                                                                                                        \
+    if (!attr_done) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(max_lds)); attr_done = true; } \
+    L2S_LAUNCH(kern, grid, block, lds, st, d);                                                                                            \
+  } while (0)
+// ... and the launcher's result
+#define IGEMM_LAUNCH_RETURN(kern, grid, block, lds, st, d)                                                                               \
+  do { IGEMM_LAUNCH(kern, grid, block, lds, lds, st, d); return l2s_check_launch(); } while (0)
+
 template <typename T, int BM, int BN, bool OUTF32>
 int launch_igemm(const l2s_conv_desc& d, hipStream_t st) {
   const int M = d.n_img * d.OH * d.OW;
   int split = 1;
-  if (BM == 64 && d.split_k > 1) {                                  // forced only: the generic kernel serves K tails and the f32 mode
-    const int K = d.KH * d.KW * d.Cin, KT = cdiv(K, ROWB / (int)sizeof(T));
-    split = splitk_factor(d, KT, (long)cdiv(M, BM) * cdiv(d.Cout, BN), false);
-  }
-  dim3 grid(cdiv(M, BM) * cdiv(d.Cout, BN), 1, split);
-  size_t lds = 2 * (BM + BN) * ROWB;
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)igemm_kernel<T, BM, BN, OUTF32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
-  L2S_LAUNCH((igemm_kernel<T, BM, BN, OUTF32>), grid, dim3(256), lds, st, d);
+  if (BM == 64 && d.split_k > 1)                                    // forced only: the generic kernel serves K tails and the f32 mode
+    split = splitk_factor(d, cdiv(d.KH * d.KW * d.Cin, ROWB / (int)sizeof(T)));
+  const size_t lds = 2 * (BM + BN) * ROWB;
+  IGEMM_LAUNCH((igemm_kernel<T, BM, BN, OUTF32>), dim3(cdiv(M, BM) * cdiv(d.Cout, BN), 1, split), dim3(256), lds, lds, st, d);
   if (split > 1) return launch_splitk_reduce<T, OUTF32>(d, split, st);
   return l2s_check_launch();
 }
@@ -2562,12 +2420,8 @@ int launch_igemm(const l2s_conv_desc& d, hipStream_t st) {
 template <typename T, int BM, int BN, int WGM, int WGN, int D, bool OUTF32>
 int launch_igemm_ring(const l2s_conv_desc& d, hipStream_t st) {
   const int M = d.n_img * d.OH * d.OW;
-  dim3 grid(cdiv(M, BM) * cdiv(d.Cout, BN));
-  size_t lds = (size_t)2 * (BM + BN) * ROWB;
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)igemm_ring_kernel<T, BM, BN, WGM, WGN, D, OUTF32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
-  L2S_LAUNCH((igemm_ring_kernel<T, BM, BN, WGM, WGN, D, OUTF32>), grid, dim3(64 * WGM * WGN), lds, st, d);
-  return l2s_check_launch();
+  const size_t lds = (size_t)2 * (BM + BN) * ROWB;
+  IGEMM_LAUNCH_RETURN((igemm_ring_kernel<T, BM, BN, WGM, WGN, D, OUTF32>), dim3(cdiv(M, BM) * cdiv(d.Cout, BN)), dim3(64 * WGM * WGN), lds, st, d);
 }
 
 template <int D, int BN, bool STAMP = false>
@@ -2583,73 +2437,47 @@ int launch_igemm_ws64(const l2s_conv_desc& d, hipStream_t st, int split = 1) {
 template <typename T, int BM, int BN, int WGM, int WGN, int D, bool OUTF32, bool TAPIN>
 int launch_igemm_sp(const l2s_conv_desc& d, hipStream_t st) {
   const int M = d.n_img * d.OH * d.OW;
-  dim3 grid(cdiv(M, BM) * cdiv(d.Cout, BN));
-  size_t lds = (size_t)3 * (BM + BN) * ROWB;
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)igemm_sp_kernel<T, BM, BN, WGM, WGN, D, OUTF32, TAPIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
-  L2S_LAUNCH((igemm_sp_kernel<T, BM, BN, WGM, WGN, D, OUTF32, TAPIN>), grid, dim3(64 * WGM * WGN), lds, st, d);
-  return l2s_check_launch();
+  const size_t lds = (size_t)3 * (BM + BN) * ROWB;
+  IGEMM_LAUNCH_RETURN((igemm_sp_kernel<T, BM, BN, WGM, WGN, D, OUTF32, TAPIN>), dim3(cdiv(M, BM) * cdiv(d.Cout, BN)), dim3(64 * WGM * WGN), lds, st, d);
 }
 
 int launch_roialign_block0(const l2s_roi_block0_desc& d, hipStream_t st) {
   const size_t lds = (size_t)d.P * d.P * d.C * 2 + 64 * sizeof(RoiTaps);   // the crop + the sample table
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)roialign_block0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_done = true; }
-  L2S_LAUNCH(roialign_block0_kernel, dim3(d.R), dim3(512), lds, st, d);
+  IGEMM_LAUNCH(roialign_block0_kernel, dim3(d.R), dim3(512), lds, 160 * 1024, st, d);
   return l2s_check_launch();
 }
 
 template <int D>
 int launch_igemm_ks64(const l2s_conv_desc& d, hipStream_t st) {
   const int M = d.n_img * d.OH * d.OW;
-  dim3 grid(cdiv(M, 64) * cdiv(d.Cout, 64));
   const size_t lds = (size_t)D * 128 * 256;
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)igemm_ks64_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
-  L2S_LAUNCH((igemm_ks64_kernel<D>), grid, dim3(512), lds, st, d);
-  return l2s_check_launch();
+  IGEMM_LAUNCH_RETURN((igemm_ks64_kernel<D>), dim3(cdiv(M, 64) * cdiv(d.Cout, 64)), dim3(512), lds, st, d);
 }
 
 template <int BN, int PR, int NS>
 int launch_igemm_p3(const l2s_conv_desc& d, hipStream_t st) {
   const int M = d.n_img * d.OH * d.OW;
-  dim3 grid(cdiv(M, 128) * cdiv(d.Cout, BN));
   const size_t lds = (size_t)NS * 4 * ((PR / 16 + 9 * BN / 16 + 3) / 4) * 1024;
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)igemm_p3_kernel<BN, PR, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
-  L2S_LAUNCH((igemm_p3_kernel<BN, PR, NS>), grid, dim3(512), lds, st, d);
-  return l2s_check_launch();
+  IGEMM_LAUNCH_RETURN((igemm_p3_kernel<BN, PR, NS>), dim3(cdiv(M, 128) * cdiv(d.Cout, BN)), dim3(512), lds, st, d);
 }
 
 template <int BM, int BN, bool STAMP = false>
 int launch_igemm_dma(const l2s_conv_desc& d, hipStream_t st) {
   const int M = d.n_img * d.OH * d.OW;
-  dim3 grid(cdiv(M, BM) * cdiv(d.Cout, BN));
   const size_t lds = (size_t)3 * (BM + BN) * ROWB + (STAMP ? 8192 : 0);
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)igemm_dma_kernel<BM, BN, STAMP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
-  L2S_LAUNCH((igemm_dma_kernel<BM, BN, STAMP>), grid, dim3(512), lds, st, d);
-  return l2s_check_launch();
+  IGEMM_LAUNCH_RETURN((igemm_dma_kernel<BM, BN, STAMP>), dim3(cdiv(M, BM) * cdiv(d.Cout, BN)), dim3(512), lds, st, d);
 }
 
 int launch_igemm_dma196(const l2s_conv_desc& d, hipStream_t st) {
   const int M = d.n_img * d.OH * d.OW;
-  dim3 grid(cdiv(M, T196) * cdiv(d.Cout, 128));
   const size_t lds = (size_t)3 * (256 + 128) * ROWB;
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)igemm_dma196_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
-  L2S_LAUNCH(igemm_dma196_kernel, grid, dim3(512), lds, st, d);
-  return l2s_check_launch();
+  IGEMM_LAUNCH_RETURN(igemm_dma196_kernel, dim3(cdiv(M, T196) * cdiv(d.Cout, 128)), dim3(512), lds, st, d);
 }
 
 int launch_igemm_dma256(const l2s_conv_desc& d, hipStream_t st) {
   const int M = d.n_img * d.OH * d.OW;
-  dim3 grid(cdiv(M, 256) * cdiv(d.Cout, 256));
   const size_t lds = (size_t)3 * 512 * 64 + 8 * 4096;     // the ring + 4 KiB of epilogue staging per wave = 128 KiB
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)igemm_dma256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
-  L2S_LAUNCH(igemm_dma256_kernel, grid, dim3(512), lds, st, d);
-  return l2s_check_launch();
+  IGEMM_LAUNCH_RETURN(igemm_dma256_kernel, dim3(cdiv(M, 256) * cdiv(d.Cout, 256)), dim3(512), lds, st, d);
 }
 
 template <int BM, int BN>
@@ -2659,11 +2487,10 @@ int launch_igemm_pdma(const l2s_conv_desc& d, hipStream_t st) {
   const int cap = l2s_knobs::pdma_wgs > 0 ? (l2s_knobs::pdma_wgs & ~7) : 256;  // (tools: fewer resident workgroups than CUs leaves whole CUs to the other queues)
   const int grid = G < cap ? ((G + 7) & ~7) : cap;     // one resident workgroup per CU, a multiple of 8 (the XCD-aware tile order)
   const size_t lds = (size_t)3 * (BM + BN) * ROWB + 8 * 2048;      // the ring + 2 KiB of epilogue staging per wave = 160 KiB
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)igemm_pdma_kernel<BM, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
-  L2S_LAUNCH((igemm_pdma_kernel<BM, BN>), dim3(grid), dim3(512), lds, st, d);
-  return l2s_check_launch();
+  IGEMM_LAUNCH_RETURN((igemm_pdma_kernel<BM, BN>), dim3(grid), dim3(512), lds, st, d);
 }
+#undef IGEMM_LAUNCH_RETURN
+#undef IGEMM_LAUNCH
 
 }  // namespace
 
@@ -2706,12 +2533,11 @@ static ConvPlan conv_plan(const l2s_conv_desc* d, int dtype, bool* tapin_out) {
     const bool dma_ok = bf && !f32o && KT >= 3 && d->KH <= 3 && d->KW <= 3;
     // split-K over workgroups (slabs + ordered reduce): forced by the caller, or chosen for few-tile / long-K launches (splitk_factor)
     if (algo == L2S_ALGO_WS64_STAMPED && bf && !f32o && tile == 64) return PLAN_WS64;   // instrumented build (tools/ws64_stamps.py)
-    if (tile == 64 && (algo == L2S_ALGO_AUTO || algo == L2S_ALGO_STAGED) && splitk_factor(*d, KT, tiles64, bf && !f32o) > 1)
+    if (tile == 64 && (algo == L2S_ALGO_AUTO || algo == L2S_ALGO_STAGED) && splitk_factor(*d, KT) > 1)
       return (bf && !f32o) ? PLAN_WS64_SPLITK : PLAN_GENERIC64;
     // persistent LDS-DMA tile: plain GEMMs (1x1 / stride 1) whose 256x128 tiles need several rounds of workgroups (layer4 on the RoIs, N >= 1024)
-    const bool pdma_ok = bf && !f32o && ntaps == 1 && d->stride == 1 && d->pad == 0 && KT >= 3 && !(d->flags & (L2S_CONV_SCATTER | L2S_CONV_DECONV2X2)) &&
-                         d->IH == d->OH && d->IW == d->OW && !(d->ldy & 3) && !(d->ldadd & 3) && !(d->ldref & 3) && !(d->Cout & 3) &&
-                         M * d->ldy * 2 < (1L << 31) && (!d->add || M * d->ldadd * 2 < (1L << 31)) && (!d->ref || M * d->ldref * 2 < (1L << 31));
+    const bool pdma_ok = bf && !f32o && ntaps == 1 && d->stride == 1 && d->pad == 0 && KT >= 3 && igemm_rows31(*d, M) &&
+                         d->IH == d->OH && d->IW == d->OW && !(d->ldy & 3) && !(d->ldadd & 3) && !(d->ldref & 3) && !(d->Cout & 3);
     // (on request only: measured 69 / 99 / 78 us against 65 / 92 / 84 us of the one-shot tiles on layer4's 1x1-out / downsample / downsample
     // data-gradient launches - the two wave groups write their sub-tiles out in different slots, and each waits for the other's stores)
     if (pdma_ok && algo == L2S_ALGO_PDMA) return PLAN_PDMA256;
@@ -2725,9 +2551,7 @@ static ConvPlan conv_plan(const l2s_conv_desc* d, int dtype, bool* tapin_out) {
     // against 64.1 / 61.6 us for the 3x3 and 32.5 against 33.8 us for the 1x1 - 2-4 % for 19 % less work per CU, because with all 256 CUs multiplying
     // the chip holds a lower clock (the loop is power-bound) - and the step is 1 % SLOWER with it (213.8 against 216.1 img/s, x2):
     // the 60 CUs the 256-row grid leaves idle are where the caption branch and the other queues run.
-    const bool d196_ok = dma_ok && !(d->flags & (L2S_CONV_DECONV2X2 | L2S_CONV_SCATTER)) && !(d->ldy & 7) && !(d->ldadd & 7) && !(d->ldref & 7) && !(d->Cout & 7) &&
-                         !((uintptr_t)d->y & 15) && !((uintptr_t)d->add & 15) && !((uintptr_t)d->ref & 15) && !((uintptr_t)d->bias & 15) &&
-                         M * d->ldy * 2 < (1L << 31) && (!d->add || M * d->ldadd * 2 < (1L << 31)) && (!d->ref || M * d->ldref * 2 < (1L << 31));
+    const bool d196_ok = dma_ok && igemm_plain(*d, M);
     if (d196_ok && algo == L2S_ALGO_DMA196) return PLAN_DMA196;
     if (dma_ok && (algo == L2S_ALGO_DMA || (algo == L2S_ALGO_AUTO && (tile == 224 || tile == 256)))) return PLAN_DMA256;
     if (dma_ok && algo == L2S_ALGO_DMA_STAMPED) return PLAN_DMA256_STAMPED;
@@ -2791,6 +2615,8 @@ extern "C" int l2s_conv_igemm(const l2s_conv_desc* d, int dtype, hipStream_t str
   }
 #define BYT(CALL_BF, CALL_F32) (dtype == L2S_BF16 ? (CALL_BF) : (CALL_F32))
 #define OUT(NAME, T, ...) (f32o ? NAME<T, __VA_ARGS__, true>(dd, stream) : NAME<T, __VA_ARGS__, false>(dd, stream))
+#define OUT_TAP(NAME, T, ...) (tapin ? (f32o ? NAME<T, __VA_ARGS__, true, true>(dd, stream) : NAME<T, __VA_ARGS__, false, true>(dd, stream)) \
+                                     : (f32o ? NAME<T, __VA_ARGS__, true, false>(dd, stream) : NAME<T, __VA_ARGS__, false, false>(dd, stream)))
   switch (plan) {
     case PLAN_PDMA256: return launch_igemm_pdma<256, 128>(dd, stream);
     case PLAN_DMA256X256: return launch_igemm_dma256(dd, stream);
@@ -2806,20 +2632,9 @@ extern "C" int l2s_conv_igemm(const l2s_conv_desc* d, int dtype, hipStream_t str
     case PLAN_WS64:
       if (d->algo == L2S_ALGO_WS64_STAMPED) return launch_igemm_ws64<3, 64, true>(dd, stream);
       return launch_igemm_ws64<3, 64>(dd, stream);
-    case PLAN_WS64_SPLITK: {
-      const int M = d->n_img * d->OH * d->OW, KT = d->KH * d->KW * d->Cin / 64;
-      return launch_igemm_ws64<3, 64>(dd, stream, splitk_factor(dd, KT, (long)cdiv(M, 64) * cdiv(d->Cout, 64), true));
-    }
-    case PLAN_SP224:
-      if (tapin) return BYT((f32o ? launch_igemm_sp<bf16_t, 224, 128, 2, 4, 2, true, true>(dd, stream) : launch_igemm_sp<bf16_t, 224, 128, 2, 4, 2, false, true>(dd, stream)),
-                            (f32o ? launch_igemm_sp<float, 224, 128, 2, 4, 2, true, true>(dd, stream) : launch_igemm_sp<float, 224, 128, 2, 4, 2, false, true>(dd, stream)));
-      return BYT((f32o ? launch_igemm_sp<bf16_t, 224, 128, 2, 4, 2, true, false>(dd, stream) : launch_igemm_sp<bf16_t, 224, 128, 2, 4, 2, false, false>(dd, stream)),
-                 (f32o ? launch_igemm_sp<float, 224, 128, 2, 4, 2, true, false>(dd, stream) : launch_igemm_sp<float, 224, 128, 2, 4, 2, false, false>(dd, stream)));
-    case PLAN_SP256:
-      if (tapin) return BYT((f32o ? launch_igemm_sp<bf16_t, 256, 128, 4, 2, 2, true, true>(dd, stream) : launch_igemm_sp<bf16_t, 256, 128, 4, 2, 2, false, true>(dd, stream)),
-                            (f32o ? launch_igemm_sp<float, 256, 128, 4, 2, 2, true, true>(dd, stream) : launch_igemm_sp<float, 256, 128, 4, 2, 2, false, true>(dd, stream)));
-      return BYT((f32o ? launch_igemm_sp<bf16_t, 256, 128, 4, 2, 2, true, false>(dd, stream) : launch_igemm_sp<bf16_t, 256, 128, 4, 2, 2, false, false>(dd, stream)),
-                 (f32o ? launch_igemm_sp<float, 256, 128, 4, 2, 2, true, false>(dd, stream) : launch_igemm_sp<float, 256, 128, 4, 2, 2, false, false>(dd, stream)));
+    case PLAN_WS64_SPLITK: return launch_igemm_ws64<3, 64>(dd, stream, splitk_factor(dd, d->KH * d->KW * d->Cin / 64));
+    case PLAN_SP224: return BYT(OUT_TAP(launch_igemm_sp, bf16_t, 224, 128, 2, 4, 2), OUT_TAP(launch_igemm_sp, float, 224, 128, 2, 4, 2));
+    case PLAN_SP256: return BYT(OUT_TAP(launch_igemm_sp, bf16_t, 256, 128, 4, 2, 2), OUT_TAP(launch_igemm_sp, float, 256, 128, 4, 2, 2));
     case PLAN_RING128X64: return launch_igemm_ring<bf16_t, 128, 64, 2, 2, 2, false>(dd, stream);
     case PLAN_RING128: return BYT(OUT(launch_igemm_ring, bf16_t, 128, 128, 2, 2, 2), OUT(launch_igemm_ring, float, 128, 128, 2, 2, 2));
     // 64x64 ring tile: depth 2 with the fragment reads ahead of the LDS fill for bf16 (fp32-output launches), depth 4 for f32
@@ -2830,6 +2645,7 @@ extern "C" int l2s_conv_igemm(const l2s_conv_desc* d, int dtype, hipStream_t str
   }
 #undef BYT
 #undef OUT
+#undef OUT_TAP
 }
 
 extern "C" int l2s_roialign_block0_fwd(const l2s_roi_block0_desc* d, hipStream_t stream) {

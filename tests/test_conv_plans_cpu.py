@@ -61,7 +61,7 @@ def test_table_reaches_every_plan():
 def test_dense_and_other_branch_per_plan():
     """each plan has a case on densely pitched, aligned operands (the LDS-staged or vector epilogue) and one on the other branch: Cout % 8,
     Cout % 4, an odd pitch, or a form whose bias / add / ref view starts 4 bytes into its buffer.  The 196-row tile has no other branch to
-    reach: the planner admits nothing but what its staged epilogue takes (d196_ok in conv_plan() is the kernel's `plain`), so every layout
+    reach: the planner admits nothing but what its staged epilogue takes (d196_ok in conv_plan() calls igemm_plain(), the predicate the kernels call), so every layout
     that would break it has to land on the fallback instead"""
     dense, other = set(), set()
     for c in CU.CASES:
