@@ -2,11 +2,14 @@
 // steps of the captioner.  One workgroup per launch, like l2s_detect_select: a decision is a few thousand values, and what matters is that
 // the next step's launches never wait for the host.
 //   l2s_decode_pick            AttModel.py:172-201    argmax or inverse-CDF draw of one row, the finished flag, the next input token
+//   l2s_decode_pick_rows       that argmax for every row of a batch of detections (one workgroup per row; the same two device functions, so
+//                              a row decides what l2s_decode_pick decides on it), or the log-probability of a forced token
 //   l2s_decode_beam_step       CaptionModel.py:27-121 beam_step + the completion loop for one t
 //   l2s_mask_resize_nearest    a predicted canvas at the blob's size, by the rule of the loader's ground-truth masks
 #include "common.h"
 #include "../../include/lang2seg_hip.h"
 #include "pil_resize.h"
+#include "rows.h"
 #include <climits>
 #include <cmath>
 
@@ -34,7 +37,38 @@ __device__ __forceinline__ void wave_best(float& bv, int& bk) {
   }
 }
 
-// ---------------------------------------------------------------- l2s_decode_pick
+// ---------------------------------------------------------------- l2s_decode_pick, l2s_decode_pick_rows
+// the log-softmax of one row x[V1] by a workgroup of DEC_T threads is (x[k] - m) - ls: the maximum and the log of the sum (red: 4 floats)
+__device__ __forceinline__ void row_max_logsum(const float* x, int V1, float* red, float& m, float& ls) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x;
+  m = -INFINITY;
+  for (int k = tid; k < V1; k += DEC_T) m = fmaxf(m, x[k]);
+  m = block_max(m, red);
+  float s = 0.f;
+  for (int k = tid; k < V1; k += DEC_T) s += expf(x[k] - m);
+  s = block_sum(s, red);
+  ls = logf(s);
+}
+// the greedy pick of that workgroup: the best word of each thread, of each wave, then of the four waves in order (wv, wk: 4 each).  The
+// result is the same in every thread; all NaN: no candidate, word 0
+__device__ __forceinline__ int block_argmax(const float* x, int V1, float m, float ls, float* wv, int* wk) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x;
+  float bv = 0.f;
+  int bk = INT_MAX;
+  for (int k = tid; k < V1; k += DEC_T) {
+    const float lp = (x[k] - m) - ls;
+    if (dec_better(lp, k, bv, bk)) { bv = lp; bk = k; }
+  }
+  wave_best(bv, bk);
+  if ((tid & 63) == 0) { wv[tid >> 6] = bv; wk[tid >> 6] = bk; }
+  __syncthreads();
+  for (int w = 0; w < DEC_T / 64; ++w)
+    if (w == 0 || dec_better(wv[w], wk[w], bv, bk)) { bv = wv[w]; bk = wk[w]; }
+  return bk == INT_MAX ? 0 : bk;
+}
+
 __global__ __launch_bounds__(DEC_T) void decode_pick_kernel(const float* logits, int V1, int t, int sample_max, float inv_temp, const float* u_in,
                                                             const uint64_t* seed_dev, uint64_t salt, int* finished, int64_t* seq,
                                                             float* seq_logprobs, int64_t* next_token) {
@@ -45,27 +79,11 @@ __global__ __launch_bounds__(DEC_T) void decode_pick_kernel(const float* logits,
   __shared__ int wk[4];
   __shared__ int s_first, s_last;
   const int tid = threadIdx.x;
-  float m = -INFINITY;
-  for (int k = tid; k < V1; k += DEC_T) m = fmaxf(m, logits[k]);
-  m = block_max(m, red);
-  float s = 0.f;
-  for (int k = tid; k < V1; k += DEC_T) s += expf(logits[k] - m);
-  s = block_sum(s, red);
-  const float ls = logf(s);
+  float m, ls;
+  row_max_logsum(logits, V1, red, m, ls);
   int pick = 0;
   if (sample_max) {
-    float bv = 0.f;
-    int bk = INT_MAX;
-    for (int k = tid; k < V1; k += DEC_T) {
-      const float lp = (logits[k] - m) - ls;
-      if (dec_better(lp, k, bv, bk)) { bv = lp; bk = k; }
-    }
-    wave_best(bv, bk);
-    if ((tid & 63) == 0) { wv[tid >> 6] = bv; wk[tid >> 6] = bk; }
-    __syncthreads();
-    for (int w = 0; w < DEC_T / 64; ++w)
-      if (w == 0 || dec_better(wv[w], wk[w], bv, bk)) { bv = wv[w]; bk = wk[w]; }
-    pick = bk == INT_MAX ? 0 : bk;                      // (all NaN: no candidate)
+    pick = block_argmax(logits, V1, m, ls, wv, wk);
   } else {
     // every thread owns a run of consecutive words: cdf(k) = [sum of the runs before, left to right] + [running sum inside the run], the
     // same roundings wherever it is evaluated, so the cdf is monotone and its last value is `total`
@@ -108,6 +126,38 @@ __global__ __launch_bounds__(DEC_T) void decode_pick_kernel(const float* logits,
     seq_logprobs[t] = fin ? 0.f : (logits[pick] - m) - ls;
     *next_token = tok;
     *finished = fin | (tok == 0);
+  }
+}
+// one workgroup per live row (rows.h): that greedy decision, or a forced token and its log-probability
+__global__ __launch_bounds__(DEC_T) void decode_pick_rows_kernel(const float* logits, int ld, int V1, int row0, const int* __restrict__ count, int t, int T,
+                                                                 const int64_t* forced, int* finished, int64_t* seq, float* logprobs,
+                                                                 int64_t* next_token, float* sum) {
+#pragma clang fp contract(off)
+  __shared__ float red[4];
+  __shared__ float wv[4];
+  __shared__ int wk[4];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  if (!row_live(r, row0, count)) return;
+  const float* x = logits + (long)r * ld;
+  float m, ls;
+  row_max_logsum(x, V1, red, m, ls);
+  int pick = 0;
+  if (forced) {
+    const int64_t f = *forced;
+    pick = f < 0 ? 0 : (f >= V1 ? V1 - 1 : (int)f);      // (a token outside the table: clamped, never an address)
+  } else {
+    pick = block_argmax(x, V1, m, ls, wv, wk);
+  }
+  if (tid == 0) {
+    // teacher forcing has no finished rows: the expression is scored to its end (AttModel.forward with the criterion's mask all ones)
+    const int fin = (forced || t == 0) ? 0 : finished[r];
+    const int tok = fin ? 0 : pick;
+    seq[(long)r * T + t] = tok;
+    const float lp = fin ? 0.f : (x[pick] - m) - ls;
+    logprobs[(long)r * T + t] = lp;
+    if (sum) sum[r] = t == 0 ? lp : sum[r] + lp;           // the row's joint log-probability, added up left to right
+    next_token[r] = tok;
+    finished[r] = fin | (tok == 0);
   }
 }
 
@@ -247,6 +297,14 @@ extern "C" int l2s_decode_pick(const float* logits, int V1, int t, int sample_ma
     return L2S_EINVAL;
   L2S_LAUNCH(decode_pick_kernel, dim3(1), dim3(DEC_T), 0, s, logits, V1, t, sample_max, sample_max ? 1.f : 1.f / temperature, u_in, seed_dev, salt,
              finished, seq, seq_logprobs, next_token);
+  return l2s_check_launch();
+}
+extern "C" int l2s_decode_pick_rows(const float* logits, int ld_logits, int V1, int rows, int row0, const int* count, int t, int T,
+                                    const int64_t* forced, int* finished, int64_t* seq, float* logprobs, int64_t* next_token, float* sum,
+                                    hipStream_t s) {
+  if (!logits || V1 < 1 || ld_logits < V1 || rows < 1 || row0 < 0 || t < 0 || t >= T || !finished || !seq || !logprobs || !next_token) return L2S_EINVAL;
+  L2S_LAUNCH(decode_pick_rows_kernel, dim3(rows), dim3(DEC_T), 0, s, logits, ld_logits, V1, row0, count, t, T, forced, finished, seq, logprobs,
+             next_token, sum);
   return l2s_check_launch();
 }
 

@@ -3,6 +3,8 @@
 // channel-contiguous (NHWC) accesses, grid-stride loops capped at ~8 blocks/CU.
 #include "common.h"
 #include "../../include/lang2seg_hip.h"
+#include "pool_bins.h"
+#include "rows.h"
 
 namespace {
 
@@ -415,14 +417,19 @@ __global__ void avgpool_bwd_bf16x8_kernel(const bf16_t* dy, bf16_t* dx, const bf
   }
 }
 
-__device__ __forceinline__ int bin_lo(int i, int n_in, int n_out) { return (i * n_in) / n_out; }
-__device__ __forceinline__ int bin_hi(int i, int n_in, int n_out) { return ((i + 1) * n_in + n_out - 1) / n_out; }
-
-__global__ void adaptive_pool_fwd_kernel(const void* x, const float* pm, void* y, int H, int W, int C, int OH, int OW, int ldy, int dt) {
+// y[bin][c] = the mean of x over the bin, under the pixel mask pm where there is one.  ROWS (l2s_adaptive_pool_rows, one row per detection):
+// row r = blockIdx.z of pm [rows][H * W] and y [rows][OH * OW][ldy], dead rows return (rows.h); without masks every row is the same pooling,
+// so it is summed once (gridDim.z = 1) and stored to every live row.  The single-row form is r = 0 with the row terms folded away.
+template <bool ROWS>
+__device__ __forceinline__ void adaptive_pool_fwd(const void* x, const float* pm, void* y, int rows, int row0, const int* count, int H, int W, int C,
+                                                  int OH, int OW, int ldy, int dt) {
   const int bin = blockIdx.y, oy = bin / OW, ox = bin - oy * OW;
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  const int r = ROWS ? blockIdx.z : 0;
   if (c >= C) return;
+  if (ROWS && pm && !row_live(r, row0, count)) return;
   const int y0 = bin_lo(oy, H, OH), y1 = bin_hi(oy, H, OH), x0 = bin_lo(ox, W, OW), x1 = bin_hi(ox, W, OW);
+  if (pm) pm += (long)r * H * W;
   float s = 0.f;
   for (int yy = y0; yy < y1; ++yy)
     for (int xx = x0; xx < x1; ++xx) {
@@ -430,7 +437,21 @@ __global__ void adaptive_pool_fwd_kernel(const void* x, const float* pm, void* y
       if (pm) v *= pm[yy * W + xx];
       s += v;
     }
-  stx(y, (long)bin * ldy + c, dt, s / (float)((y1 - y0) * (x1 - x0)));
+  const float v = s / (float)((y1 - y0) * (x1 - x0));
+  const long rs = (long)OH * OW * ldy;
+  if (!ROWS || pm) {
+    stx(y, r * rs + (long)bin * ldy + c, dt, v);
+  } else {
+    const int n = live_rows(rows, row0, count);
+    for (int q = 0; q < n; ++q) stx(y, q * rs + (long)bin * ldy + c, dt, v);
+  }
+}
+__global__ void adaptive_pool_fwd_kernel(const void* x, const float* pm, void* y, int H, int W, int C, int OH, int OW, int ldy, int dt) {
+  adaptive_pool_fwd<false>(x, pm, y, 1, 0, nullptr, H, W, C, OH, OW, ldy, dt);
+}
+__global__ void adaptive_pool_rows_kernel(const void* x, const float* pm, void* y, int rows, int row0, const int* count, int H, int W, int C, int OH,
+                                          int OW, int ldy, int dt) {
+  adaptive_pool_fwd<true>(x, pm, y, rows, row0, count, H, W, C, OH, OW, ldy, dt);
 }
 
 __global__ void adaptive_pool_bwd_kernel(const void* dy, int lddy, int off_all, int off_mask, const float* pm, void* dx,
@@ -516,12 +537,9 @@ __global__ void mask_downsample_kernel(const uint8_t* mask, float* out, int H, i
   const int o = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (o >= h * w) return;
   const int oy = o / w, ox = o - oy * w;
-  const int y0 = bin_lo(oy, H, h), y1 = bin_hi(oy, H, h), x0 = bin_lo(ox, W, w), x1 = bin_hi(ox, W, w);
-  const int bw = x1 - x0, n = (y1 - y0) * bw;
-  float s = 0.f;
-  for (int i = lane; i < n; i += 64) { int yy = y0 + i / bw, xx = x0 + i % bw; s += (float)mask[(long)yy * W + xx]; }
-  s = wave_sum(s);
-  if (lane == 0) out[o] = (s / (float)n >= 0.5f) ? 1.f : 0.f;
+  const float v = wave_bin_vote([&](int yy, int xx) { return mask[(long)yy * W + xx]; }, bin_lo(oy, H, h), bin_hi(oy, H, h), bin_lo(ox, W, w),
+                                bin_hi(ox, W, w), lane);
+  if (lane == 0) out[o] = v;
 }
 
 __global__ void counter_inc_kernel(uint64_t* c) { *c += 1; }
@@ -734,6 +752,15 @@ extern "C" int l2s_avgpool_bwd(const void* dy, void* dx, const void* addend, con
 }
 extern "C" int l2s_adaptive_pool_fwd(const void* x, const float* pm, void* y, int H, int W, int C, int OH, int OW, int ldy, int dtype, hipStream_t s) {
   L2S_LAUNCH(adaptive_pool_fwd_kernel, dim3(cdiv(C, 256), OH * OW), dim3(256), 0, s, x, pm, y, H, W, C, OH, OW, ldy, dtype);
+  return l2s_check_launch();
+}
+extern "C" int l2s_adaptive_pool_rows(const void* x, const float* pm, void* y, int rows, int row0, const int* count, int H, int W, int C, int OH, int OW,
+                                      int ldy, int dtype, hipStream_t s) {
+  if (!x || !y || rows < 1 || rows > 65535 || row0 < 0 || H < 1 || W < 1 || C < 1 || OH < 1 || OW < 1 || (long)OH * OW > 65535 || ldy < C ||
+      (dtype != 0 && dtype != 1))
+    return L2S_EINVAL;
+  L2S_LAUNCH(adaptive_pool_rows_kernel, dim3(cdiv(C, 256), OH * OW, pm ? rows : 1), dim3(256), 0, s, x, pm, y, rows, row0, count, H, W, C, OH, OW, ldy,
+             dtype);
   return l2s_check_launch();
 }
 extern "C" int l2s_adaptive_pool_bwd(const void* dy, int lddy, int off_all, int off_mask, const float* pm, void* dx, const void* ref,

@@ -9,7 +9,8 @@ Two routes:
             launches per token are the same, and `count` stays on the device.
               att2in2  the head as GEMMs on rows * 196 rows (att_embed, ctx2att, P = att . W_a2c^T), then per token [embedding, i2h]
                        (greedy; scoring does both once for all n + 1 inputs) -> h2h and h2att as row-batch Linears -> the row-strided
-                       attention dots and softmax + gates (csrc/caption_rows.hip) -> logits -> decision: 8 launches a token, 6 when scoring.
+                       attention dots and softmax + gates (csrc/caption_step.hip: the train step's kernel bodies with a row index) ->
+                       logits -> decision: 8 launches a token, 6 when scoring.
               topdown  the head: att_embed and ctx2att on rows * 196 rows, fc_embed and the fc product (fcrow [rows][4 rnn_size]) on rows;
                        per token [embedding, the xt columns of att_lstm.weight_ih] (greedy; once per call when scoring) -> the attention
                        cell (l2s_lstm_cell_rows: both products on MFMA tiles of rows and the cell in one launch) -> h2att -> attention

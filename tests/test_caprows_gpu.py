@@ -3,10 +3,10 @@ single-mask kernel it restates, Network.caption_decode_rows / caption_score_rows
 (tests/golden/ref_caprows.npz, which tests/test_caprows_cpu.py ties to the numpy restatement), both routes against each other and against
 the merged single-mask path, the launch count, the features, and the detection dicts end to end.
 
-Bounds.  masks_to_map and adaptive_pool_rows: the same bits as the single-mask launches (integer counts; the same summation order).  The
-recurrent step, every log-probability and the features: FWD_TOL = 1e-5 as tests/topdown_util.py's rel_err defines it (the largest
-difference over the reference's largest magnitude), the project's bound for these kernels.  Tokens: exact.  `score` is the float32 sum of
-the returned log-probabilities, added left to right: exact.
+Bounds.  masks_to_map, adaptive_pool_rows, the two kernels of the recurrent step and decode_pick_rows: the same bits as the single-mask
+launches (a row entry is the single-mask kernel's own body with a row index).  Every log-probability of a whole route and the features:
+FWD_TOL = 1e-5 as tests/topdown_util.py's rel_err defines it (the largest difference over the reference's largest magnitude), the project's
+bound for these kernels.  Tokens: exact.  `score` is the float32 sum of the returned log-probabilities, added left to right: exact.
 
 Worst values measured on an MI355X (this file's own prints):
   rows step vs the single-row kernels      h and c 0 at every size
@@ -118,11 +118,16 @@ def test_adaptive_pool_rows_equals_adaptive_pool_fwd_per_row(C, hw, bins, dt):
 
 
 # ------------------------------------------------------------------ 3. the recurrent step on rows
-@pytest.mark.parametrize('rows', [1, 3, 65])
-@pytest.mark.parametrize('RA', [(32, 16), (512, 512)])
-def test_rows_step_equals_the_single_row_kernels(RA, rows):
+# (R, AH) x rows at the module's L, and the tails: R no multiple of 16 and AH no multiple of 64 with one wave of locations, the fixture's
+# 196 and the largest L
+STEP_CASES = [pytest.param(RA, rows, L, id='RA%d-%d' % (i, rows)) for i, RA in enumerate([(32, 16), (512, 512)]) for rows in [1, 3, 65]] + \
+             [pytest.param((20, 70), 3, nl, id='tails-L%d' % nl) for nl in (5, 196, 256)]
+
+
+@pytest.mark.parametrize('RA,rows,L', STEP_CASES)
+def test_rows_step_equals_the_single_row_kernels(RA, rows, L):
     """the two row kernels, issued in chunks of 64 rows with row0 as the network issues them, against cap_att_dots_fwd + cap_apply_gates_fwd
-    row by row on the same inputs"""
+    row by row on the same inputs: the same kernel bodies (csrc/caption_step.hip), so the same bits"""
     O = ops()
     R, AH = RA
     rs = np.random.RandomState(R + rows)
@@ -140,22 +145,21 @@ def test_rows_step_equals_the_single_row_kernels(RA, rows):
         n = min(64, rows - r0)
         O.cap_att_dots_rows(patt[r0:], att_h[r0:], aw, ab, n, L, AH, dots[r0:], cnt, r0)
         O.cap_apply_gates_rows(P[r0:], dots[r0:], b, sums[r0:], c_prev[r0:], c[r0:], h[r0:], n, L, R, cnt, r0)
+    dots_last = dots[rows - 1, :L].clone()
     # the rows at or beyond count stay as they are
     h2, c2 = torch.full((rows, R), 7.0, device=DEV), torch.full((rows, R), 7.0, device=DEV)
     O.cap_att_dots_rows(patt, att_h, aw, ab, rows, L, AH, dots, count_of(rows - 1))
     O.cap_apply_gates_rows(P, dots, b, sums, c_prev, c2, h2, rows, L, R, count_of(rows - 1))
     torch.cuda.synchronize()
     eh, ec = rel_err(h, h_ref), rel_err(c, c_ref)
-    print('rows step R %d AH %d rows %d vs the single-row kernels: h %.2e c %.2e' % (R, AH, rows, eh, ec))
-    assert eh <= FWD_TOL and ec <= FWD_TOL
-    assert bool((h2[rows - 1] == 7.0).all()) and bool((c2[rows - 1] == 7.0).all()) and (rows == 1 or rel_err(h2[:rows - 1], h_ref[:rows - 1]) <= FWD_TOL)
+    print('rows step R %d AH %d rows %d L %d vs the single-row kernels: h %.2e c %.2e' % (R, AH, rows, L, eh, ec))
+    assert same_bits(h, h_ref) and same_bits(c, c_ref)
+    assert same_bits(dots_last, dots1[:L])                             # (dots1: what the single-row kernel left for the last row)
+    assert bool((h2[rows - 1] == 7.0).all()) and bool((c2[rows - 1] == 7.0).all()) and (rows == 1 or same_bits(h2[:rows - 1], h_ref[:rows - 1]))
 
 
 # ------------------------------------------------------------------ 4. the decision per row
-@pytest.mark.parametrize('V1', [2, 21, 65, 1025])
-def test_decode_pick_rows(V1):
-    O = ops()
-    T, rows, live = 3, 5, 4
+def _pick_logits(V1, T=3, rows=5):
     rs = np.random.RandomState(V1)
     x = rs.normal(0, 3, (T, rows, V1)).astype(np.float32)
     hi = max(1, V1 // 2)
@@ -166,6 +170,14 @@ def test_decode_pick_rows(V1):
         x[1, 1] = [0.5, 0.5]                                         # (two words: the tie is between 0 and 1 -> 0, which also ends the row)
     x[0, 2, 0] = x[0, 2].max() + 2.0                                 # row 2 ends at t = 0: zeros from there, its neighbours go on
     x[2, 2, V1 - 1] = x[2, 2].max() + 5.0
+    return x, hi
+
+
+@pytest.mark.parametrize('V1', [2, 21, 65, 1025])
+def test_decode_pick_rows(V1):
+    O = ops()
+    T, rows, live = 3, 5, 4
+    x, hi = _pick_logits(V1, T, rows)
     xd = dev(x)
     lsm = DU.log_softmax(x)
     mk = lambda: (torch.full((rows,), 9, dtype=torch.int32, device=DEV), torch.full((rows, T), -7, dtype=torch.int64, device=DEV),
@@ -205,6 +217,35 @@ def test_decode_pick_rows(V1):
     for t, k in enumerate([hi, 0, V1 - 1]):
         assert (seq_h[:live, t] == k).all() and np.abs(lps_h[:live, t] - lsm[t, :live, k]).max() <= FWD_TOL * max(1.0, scale)
     assert (tok.cpu().numpy()[:live] == V1 - 1).all() and (seq_h[live:] == -7).all()
+
+
+@pytest.mark.parametrize('V1', [2, 21, 65, 1025])
+def test_decode_pick_rows_on_one_row_equals_decode_pick(V1):
+    """the greedy decision through both entries (csrc/decode.hip: one max / log-sum and one argmax for both), T = 3: row 1 of the logits
+    above (a tie: the lower index; with two words it also ends the row), row 2 (ends at t = 0), and row 1 with an all-NaN last step, where
+    nothing is a candidate and the pick is word 0.  seq, the log-probabilities, next_token and finished: the same bits after every step"""
+    O = ops()
+    T = 3
+    x, hi = _pick_logits(V1, T)
+    nan_last = x[:, 1].copy()
+    nan_last[T - 1] = np.nan
+    for name, seq_x in (('tie', x[:, 1]), ('early end', x[:, 2]), ('all-NaN step', nan_last)):
+        xd = dev(seq_x)
+        fin1, seq1, lps1, tok1 = (torch.full((1,), 9, dtype=torch.int32, device=DEV), torch.full((T,), -7, dtype=torch.int64, device=DEV),
+                                  torch.full((T,), -7.0, device=DEV), torch.full((1,), -7, dtype=torch.int64, device=DEV))
+        finr, seqr, lpsr, tokr = fin1.clone(), seq1.clone().view(1, T), lps1.clone().view(1, T), tok1.clone()
+        for t in range(T):
+            O.decode_pick(xd[t], V1, t, 1, 1.0, None, None, 0, fin1, seq1, lps1, tok1)
+            O.decode_pick_rows(xd[t:t + 1], V1, 1, t, T, finr, seqr, lpsr, tokr)
+            torch.cuda.synchronize()
+            assert same_bits(seqr[0], seq1) and same_bits(lpsr[0], lps1) and same_bits(tokr, tok1) and same_bits(finr, fin1), (name, t, seq1, seqr, lps1, lpsr)
+        s = seq1.cpu().numpy()
+        if name == 'tie':
+            assert s[1] == (hi if V1 > 2 else 0)
+        elif name == 'early end':
+            assert (s == 0).all() and int(fin1) == 1 and (lps1.cpu().numpy()[1:] == 0).all()
+        elif s[:T - 1].all():                                         # (two words: the tie ended the row before the NaN step)
+            assert s[T - 1] == 0 and int(tok1) == 0 and int(fin1) == 1 and bool(torch.isnan(lps1[T - 1]))
 
 
 # ------------------------------------------------------------------ 5. / 6. the reference's batch runs through a network
