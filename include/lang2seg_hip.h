@@ -621,6 +621,30 @@ int l2s_detect_select(const void* ws, int post, int ncls, int max_per_image, flo
 int l2s_detect_paste(const float* mask_prob, int ms, l2s_det_record* rec, const int* count, int cap, int ih, int iw, uint8_t* canvases,
                      hipStream_t s);
 
+/* ---------------------------------------------------------------- judging the detections (model/detect_device.py, csrc/select.hip) ----- */
+/* One detection against the sentence's ground truth (16 bytes): the intersection and union pixel counts of its mask with the gt
+ * mask, and whether its box hits the gt box (IoU >= 0.5). */
+typedef struct { int I; int U; int hit; int reserved; } l2s_det_gt;
+/* One rule's choice among a sentence's detections (40 bytes): its index in the list (-1: the list is empty; then cls = -1, hit = 0,
+ * I = 0, U = the gt's pixels), its class, hit, I, U and the key it won with. */
+typedef struct { int det; int cls; int hit; int reserved; long long I; long long U; double key; } l2s_det_choice;
+/* Device.  For every detection d < count[0] (clamped to cap) of canvases [cap][ih][iw] (uint8 {0, 1}, as l2s_detect_paste left them:
+ * zero outside eval_box_geometry of rec[d].box, rec[d].area set pixels): I = |canvas & gt|, U = |canvas | gt| with the gt mask [Hs][Ws]
+ * PIL-NEAREST resized to ih x iw as l2s_eval_mask_iou reads it, and hit = computeIoU_box(rec[d].box, gt_box / im_scale) >= 0.5 by
+ * l2s_eval_pick's float32 expressions; gt_area[0] = the set pixels of the resized gt.  Only the box of a detection is read:
+ * U = rec[d].area + gt_area - I, in integers.  out [cap] and gt_area [1] are accumulated into with integer atomics and must be zero on
+ * entry; rows d >= count[0] are written as zeros.  cap <= 65535, ih * iw < 2^31; L2S_EINVAL otherwise. */
+int l2s_detect_gt_iou(const uint8_t* canvases, const l2s_det_record* rec, const int* count, int cap, int ih, int iw, const uint8_t* gt, int Hs,
+                      int Ws, const float* gt_box, float im_scale, l2s_det_gt* out, int* gt_area, hipStream_t s);
+/* Device, one workgroup.  Among the detections d < count[0] (clamped to cap), ties to the lowest d, out[0] = `detector`: max rec[d].score;
+ * out[1] = `oracle`: max I / U, compared exactly (a beats b iff I_a * U_b > I_b * U_a in 64 bits; U = 0 counts as 0 / 1), key = I / U in
+ * double; and with expr (device float [cap], the expression's log-likelihood under every detection's mask) out[2] = `speaker`: max
+ * expr[d]; out[3 + k] = `rerank@lambdas[k]`: max key = log((double)score) + (double)lambdas[k] * (double)expr[d] / (per_token ? n_tok : 1),
+ * every operation rounded on its own.  lambdas: host float [n_lambda], n_lambda <= 8; n_lambda > 0 without expr is L2S_EINVAL.
+ * Scores and expr are taken to be no NaN. */
+int l2s_detect_choose(const l2s_det_record* rec, const l2s_det_gt* gt, const int* count, int cap, const int* gt_area, const float* expr,
+                      const float* lambdas, int n_lambda, int per_token, int n_tok, l2s_det_choice* out, hipStream_t s);
+
 /* ---------------------------------------------------------------- caption decoding (nets/decode.py, csrc/decode.hip) ----- */
 /* Device, one workgroup.  One decision of AttModel.sample (AttModel.py:172-201) on logits[V1]: log-softmax in f32, then
  *   sample_max != 0: the argmax (lowest index on equal values);

@@ -220,6 +220,8 @@ SIGS = {
     'l2s_detect_nms': (i32, [vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, f32, f32, vp, vp, vp]),
     'l2s_detect_select': (i32, [vp, i32, i32, i32, f32, vp, vp, vp, i32, vp, vp]),
     'l2s_detect_paste': (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp]),
+    'l2s_detect_gt_iou': (i32, [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp, f32, vp, vp, vp]),
+    'l2s_detect_choose': (i32, [vp, vp, vp, i32, vp, vp, C.POINTER(f32), i32, i32, i32, vp, vp]),
     'l2s_decode_pick': (i32, [vp, i32, i32, i32, f32, vp, vp, u64, vp, vp, vp, vp, vp]),
     'l2s_decode_beam_step': (i32, [C.POINTER(BeamStepArgs), vp]),
     'l2s_mask_resize_nearest': (i32, [vp, i32, i32, vp, i32, i32, vp]),

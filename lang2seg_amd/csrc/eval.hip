@@ -62,16 +62,8 @@ __global__ __launch_bounds__(256) void eval_pick_kernel(const float* cls_prob, c
   // detect_from_outputs on the chosen row: boxes = rois[:, 1:5] / scale, bbox_transform_inv_np, _clip_boxes (all float32)
   float o[4];
   eval_decode_box(rois + (long)row * 5, bbox_pred ? bbox_pred + (long)row * 4 * C + 4 * cls : rois, im_scale, im_h, im_w, bbox_reg, o);
-  // computeIoU_box(pred_box, gt_box / im_scale) >= 0.5 in float32, the host's order of operations
-  float g[4];
-  for (int k = 0; k < 4; ++k) g[k] = gt_box[k] / im_scale;
-  const float ix1 = fmaxf(o[0], g[0]), iy1 = fmaxf(o[1], g[1]), ix2 = fminf(o[2], g[2]), iy2 = fminf(o[3], g[3]);
-  float inter = 0.f;
-  if (ix1 < ix2 && iy1 < iy2) inter = (ix2 - ix1 + 1.f) * (iy2 - iy1 + 1.f);
-  const float a1 = (o[2] - o[0] + 1.f) * (o[3] - o[1] + 1.f), a2 = (g[2] - g[0] + 1.f) * (g[3] - g[1] + 1.f);
-  const float uni = a1 + a2 - inter;
-  const float iou = inter / uni;
-  r.roi = row; r.cls = cls; r.hit = iou >= 0.5f ? 1 : 0;
+  // computeIoU_box(pred_box, gt_box / im_scale) >= 0.5 in float32, the host's order of operations (eval_helpers.h)
+  r.roi = row; r.cls = cls; r.hit = eval_box_hit(o, gt_box, im_scale);
   for (int k = 0; k < 4; ++k) r.box[k] = o[k];
   *rec = r;
   // the mask head's RoI: np.array([pred_box]) * im_scale (float32) behind a zero batch index

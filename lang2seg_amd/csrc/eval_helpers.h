@@ -80,6 +80,21 @@ __host__ __device__ inline void eval_decode_box(const float* roi, const float* d
   }
 }
 
+// computeIoU_box(pred_box, gt_box / im_scale) >= 0.5 in float32, the host's order of operations (o: the box in the original image,
+// gt_box: x1 y1 x2 y2 in the scaled image): one text for l2s_eval_pick and l2s_detect_gt_iou
+__host__ __device__ inline int eval_box_hit(const float* o, const float* gt_box, float im_scale) {
+#pragma clang fp contract(off)
+  float g[4];
+  for (int k = 0; k < 4; ++k) g[k] = gt_box[k] / im_scale;
+  const float ix1 = fmaxf(o[0], g[0]), iy1 = fmaxf(o[1], g[1]), ix2 = fminf(o[2], g[2]), iy2 = fminf(o[3], g[3]);
+  float inter = 0.f;
+  if (ix1 < ix2 && iy1 < iy2) inter = (ix2 - ix1 + 1.f) * (iy2 - iy1 + 1.f);
+  const float a1 = (o[2] - o[0] + 1.f) * (o[3] - o[1] + 1.f), a2 = (g[2] - g[0] + 1.f) * (g[3] - g[1] + 1.f);
+  const float uni = a1 + a2 - inter;
+  const float iou = inter / uni;
+  return iou >= 0.5f ? 1 : 0;
+}
+
 #ifdef __HIPCC__
 // the first step of a paste, by a workgroup of 256 threads: bytescale of the ms x ms probabilities * 255 over their own [min, max] -> src
 __device__ inline void eval_bytescale_block(const float* prob, int mm, float* smin, float* smax, uint8_t* src) {

@@ -13,6 +13,20 @@ __host__ __device__ inline int pil_nearest_src(int k, int n_src, int n_out) {
   return v < n_src - 1 ? v : n_src - 1;
 }
 
+// the same walk for a run of consecutive outputs: pil_nearest_src(k) == pil_nearest_at(pil_nearest_xo(k)), and output k + 1's xo is
+// output k's + pil_nearest_step (the additions pil_nearest_src makes, one at a time)
+__host__ __device__ inline double pil_nearest_step(int n_src, int n_out) { return (double)n_src / (double)n_out; }
+__host__ __device__ inline double pil_nearest_xo(int k, int n_src, int n_out) {
+  const double s = pil_nearest_step(n_src, n_out);
+  double xo = 0.5 * s;
+  for (int i = 0; i < k; ++i) xo += s;
+  return xo;
+}
+__host__ __device__ inline int pil_nearest_at(double xo, int n_src) {
+  const int v = (int)xo;
+  return v < n_src - 1 ? v : n_src - 1;
+}
+
 // Pillow's 8-bit BILINEAR resample (libImaging/Resample.c: precompute_coeffs + normalize_coeffs_8bpc) of in_size -> out_size samples,
 // box (0, in_size): the taps of output sample xx.  Coefficients in float64 with support = filterscale (the antialiasing path when the
 // output is smaller), normalised by their sequential sum, then to fixed point with PRECISION_BITS = 22, rounded away from zero.

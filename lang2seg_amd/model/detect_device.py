@@ -12,7 +12,13 @@ counts its first run reported (the backbone map of forward_test_image is still t
 Optionally (detect_image describe= / expr_score=, cycle network) the caption branch on rows runs behind each sentence's detections, on the
 sentence's canvases with the detector's device count (nets/caption_rows.py): what the captioner says about every detection, and the
 teacher-forced log-likelihood of the sentence's own expression under every detection's mask.  Its results stay on the device per sentence
-and come back as one more read-back per image."""
+and come back as one more read-back per image.
+
+Optionally (detect_image gt_masks= / eval_split_device judge=, rerank=) every detection is judged against the sentence's ground truth on
+the device (csrc/select.hip: l2s_detect_gt_iou, l2s_detect_choose, behind the rows stage, whose score it reads): I, U and hit per
+detection, and per rule (detector, oracle, speaker, rerank@lambda) the detection it picks.  One more read-back per image."""
+import math
+
 import numpy as np
 import torch
 
@@ -94,6 +100,7 @@ class _RowsStage(object):
         if self.expr_score:
             r = net.caption_score_rows(att, fc, self.tokens[i], rows=cap, count=written)
             out['elp'], out['score'] = r['logprobs'].clone(), r['score'].clone()
+            self.net_score = r['score']                            # the network's buffer: the judge stage reads it in stream order
         return out
 
     KEYS = (('seq', np.int64), ('lp', np.float32), ('elp', np.float32), ('score', np.float32))
@@ -126,13 +133,89 @@ class _RowsStage(object):
         return p
 
 
+def check_rerank(rerank):
+    """the lambdas of the re-ranking rules as a list of floats.  ValueError (naming rerank / --rerank) on an entry that is no finite
+    float, on more than ops.DET_MAX_LAMBDA entries and on an entry given twice (the rules are named by their lambda)"""
+    out = []
+    for v in (rerank or ()):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            f = float('nan')
+        if not math.isfinite(f) or not math.isfinite(float(np.float32(f))):
+            raise ValueError('rerank (--rerank): every entry is a finite float, got %r' % (v,))
+        out.append(f)                                              # (the kernel takes them rounded to float32)
+    if len(out) > O.DET_MAX_LAMBDA:
+        raise ValueError('rerank (--rerank): at most %d entries, got %d' % (O.DET_MAX_LAMBDA, len(out)))
+    if len(set(out)) != len(out):
+        raise ValueError('rerank (--rerank): an entry is given twice in %r' % (list(rerank),))
+    return out
+
+
+def rule_names(lambdas, with_expr):
+    """the rules of l2s_detect_choose in the order of its records"""
+    return ['detector', 'oracle'] + (['speaker'] + ['rerank@%s' % l for l in lambdas] if with_expr else [])
+
+
+class _JudgeStage(object):
+    """every detection of a sentence against its ground truth, and one detection per rule (csrc/select.hip), behind the rows stage.
+    gt_masks: per sentence a device uint8 [Hs][Ws] mask; gt_boxes: device f32 [S][4] (scaled image); n_tok: per sentence the
+    expression's tokens + 1.  with_expr: the rows stage scores the expression (rules speaker and rerank@lambda)"""
+
+    def __init__(self, net, gt_masks, gt_boxes, scale, n_tok, rerank=None, per_token=False, with_expr=False):
+        if getattr(net, 'variant', None) == 'vgg':
+            raise ValueError('judging detections (judge / --judge_detections, rerank / --rerank) compares masks: variant vgg has no mask branch')
+        self.lambdas = check_rerank(rerank)
+        if self.lambdas and not with_expr:
+            raise ValueError('rerank (--rerank) weighs the expression\'s log-likelihood: it needs expr_score (--expr_score 1)')
+        if per_token and not self.lambdas:
+            raise ValueError('per_token (--rerank_per_token) divides the re-ranking term: it needs rerank (--rerank)')
+        self.net, self.gt_masks, self.gt_boxes, self.scale, self.n_tok = net, gt_masks, gt_boxes, scale, [int(v) for v in n_tok]
+        self.per_token, self.with_expr = bool(per_token), bool(with_expr)
+        self.names = rule_names(self.lambdas, self.with_expr)
+
+    def one(self, i):
+        """the stage of sentence i alone (its re-run)"""
+        return _JudgeStage(self.net, [self.gt_masks[i]], self.gt_boxes[i:i + 1], self.scale, [self.n_tok[i]], self.lambdas, self.per_token,
+                           self.with_expr)
+
+    def stride(self, cap):
+        """int32 words of one sentence: the choice records (8-byte aligned: the stride is even), cap l2s_det_gt rows, gt_area, a pad"""
+        return len(self.names) * (O.DET_CHOICE_BYTES // 4) + cap * (O.DET_GT_BYTES // 4) + 2
+
+    def alloc(self, S, cap):
+        """the image's device array, zeroed once (the kernel accumulates; every sentence's part is used once)"""
+        return torch.zeros((S * self.stride(cap),), dtype=torch.int32, device=torch.device(self.net.device))
+
+    def _views(self, arr, i, cap):
+        b, nc = i * self.stride(cap), len(self.names) * (O.DET_CHOICE_BYTES // 4)
+        ng = cap * (O.DET_GT_BYTES // 4)
+        return arr[b:b + nc], arr[b + nc:b + nc + ng], arr[b + nc + ng:b + nc + ng + 1]
+
+    def run(self, i, arr, canvases, rec, count, cap, expr):
+        """two launches on sentence i's canvases and records; expr: the rows stage's score buffer, or None"""
+        choice, rows, area = self._views(arr, i, cap)
+        O.detect_gt_iou(canvases, rec, count, self.gt_masks[i], self.gt_boxes[i], self.scale, rows, area, clear=False)
+        O.detect_choose(rec, rows, count, cap, area, choice, expr if self.with_expr else None, self.lambdas if self.with_expr else (),
+                        self.per_token, self.n_tok[i])
+
+    def host(self, arr, i, cap):
+        """sentence i of the read-back -> ((I, U, hit) per row, gt_area, {rule: dict})"""
+        choice, rows, area = self._views(arr, i, cap)
+        det, cls, hit, I, U, key = O.det_choice_fields(choice)
+        rules = {name: dict(det=int(det[k]), category_id=int(cls[k]), hit=int(hit[k]), I=int(I[k]), U=int(U[k]), key=float(key[k]))
+                 for k, name in enumerate(self.names)}
+        return O.det_gt_fields(rows), int(area[0]), rules
+
+
 class _Detector(object):
     """the device side of one image's detections: per sentence `cap` records, the count and the spans in one int32 array (one read-back),
     the image's run-length pool"""
 
-    def __init__(self, net, S, scale, ih, iw, max_per_image, thresh, cap=None, pool_words=None, capture=None, stage=None):
+    def __init__(self, net, S, scale, ih, iw, max_per_image, thresh, cap=None, pool_words=None, capture=None, stage=None, judge=None):
         self.net, self.S, self.scale, self.ih, self.iw = net, S, scale, ih, iw
         self.stage, self.stage_out = stage, [None] * S
+        self.judge = judge
         self.max_per_image, self.thresh = int(max_per_image), float(thresh)
         self.cap = cap = default_cap(max_per_image) if cap is None else int(cap)
         self.with_masks = getattr(net, 'variant', None) != 'vgg'
@@ -144,6 +227,8 @@ class _Detector(object):
         if self.with_masks:
             words = S * _pool_budget(cap, iw) if pool_words is None else int(pool_words)
             self.pool = torch.empty((max(words, 1),), dtype=torch.int32, device=dev)
+        if judge is not None:
+            self.jmeta = judge.alloc(S, cap)
 
     def _views(self, meta, i):
         b = 1 + i * self.stride
@@ -161,24 +246,38 @@ class _Detector(object):
                               spans=spans, pool=self.pool if self.with_masks else None, cursor=self.meta[0:1])
         if self.stage is not None:                                # on this sentence's canvases, before the next sentence overwrites them
             self.stage_out[i] = self.stage.run(i, out['canvases'], self.cap, self.ih, self.iw, count[0:1])
+        if self.judge is not None:                                # behind the rows stage: it reads that stage's score
+            self.judge.run(i, self.jmeta, out['canvases'], rec, count[0:1], self.cap,
+                           self.stage.net_score if self.judge.with_expr else None)
         if cap_in is not None:
             if self.with_masks:
                 cap_in['mask_prob'] = out['mask_prob'].clone()
             self.capture.append(cap_in)
 
-    def collect(self, file_name, resentence, extra=None):
+    def collect(self, file_name, resentence, extra=None, selection=None):
         """the read-back -> one list of dicts per sentence.  resentence(i): forward_test_sentence of sentence i again (a sentence that did
-        not fit its buffers runs again with the sizes its counts ask for)."""
+        not fit its buffers runs again with the sizes its counts ask for).  selection: with a judge stage, a list that receives per
+        sentence {file_name, sent_index, gt_area, rules: {rule: {det, category_id, hit, I, U, key}}}."""
         meta = self.meta.cpu().numpy()
         pool = self.pool[:int(meta[0])].cpu().numpy().view('<u4') if self.with_masks else None
         rows = None if self.stage is None else self.stage.read_back(self.stage_out)
+        jm = None if self.judge is None else self.jmeta.cpu().numpy()
+
+        def judged(det, arr, k, i):
+            if arr is None:
+                return None
+            gt_rows, gt_area, rules = det.judge.host(arr, k, det.cap)
+            if selection is not None:
+                selection.append(dict(file_name=file_name, sent_index=i, gt_area=gt_area, rules=rules))
+            return gt_rows
         out = []
         for i in range(self.S):
             count, rec, spans = self._views(meta, i)
             written, total = int(count[0]), int(count[1])
             fits = total <= self.cap and not (self.with_masks and (spans[:written, 0] < 0).any())
             if fits:
-                out.append(self._dicts(rec[:written], spans[:written], pool, file_name, i, extra, None if rows is None else rows[i]))
+                out.append(self._dicts(rec[:written], spans[:written], pool, file_name, i, extra, None if rows is None else rows[i],
+                                       gt_rows=judged(self, jm, i, i)))
                 continue
             if self.capture is not None:
                 self.capture.append(dict(rerun=i))
@@ -186,7 +285,8 @@ class _Detector(object):
             words = int(spans[:written, 1].astype(np.int64).sum()) if total <= self.cap else _pool_budget(cap, self.iw)
             while True:                                            # sizes grow with every round: the counts of `total` masks are a finite sum
                 one = _Detector(self.net, 1, self.scale, self.ih, self.iw, self.max_per_image, self.thresh, cap=cap, pool_words=words,
-                                stage=None if self.stage is None else self.stage.one(i))
+                                stage=None if self.stage is None else self.stage.one(i),
+                                judge=None if self.judge is None else self.judge.one(i))
                 one.run(0, resentence(i))
                 m1 = one.meta.cpu().numpy()
                 c1, r1, s1 = one._views(m1, 0)
@@ -197,11 +297,12 @@ class _Detector(object):
                     continue
                 p1 = one.pool[:int(m1[0])].cpu().numpy().view('<u4') if self.with_masks else None
                 out.append(self._dicts(r1[:int(c1[0])], s1[:int(c1[0])], p1, file_name, i, extra,
-                                       None if one.stage is None else one.stage.read_back(one.stage_out)[0], one.stage))
+                                       None if one.stage is None else one.stage.read_back(one.stage_out)[0], one.stage,
+                                       gt_rows=judged(one, None if one.judge is None else one.jmeta.cpu().numpy(), 0, i)))
                 break
         return out
 
-    def _dicts(self, rec, spans, pool, file_name, i, extra, rows=None, stage=None):
+    def _dicts(self, rec, spans, pool, file_name, i, extra, rows=None, stage=None, gt_rows=None):
         roi, cls, box, score, area = O.det_record_fields(np.ascontiguousarray(rec))
         res = []
         for k in range(rec.shape[0]):
@@ -215,6 +316,8 @@ class _Detector(object):
                 p['segmentation'] = dict(size=[self.ih, self.iw], counts=O.rle_to_string(pool[off:off + n]))
             if rows is not None:
                 p.update((stage or self.stage).fields(rows, k))
+            if gt_rows is not None:
+                p.update(I=int(gt_rows[0][k]), U=int(gt_rows[1][k]), hit=int(gt_rows[2][k]))
             res.append(p)
         return res
 
@@ -227,8 +330,19 @@ def rows_stage(net, labels, describe, expr_score, ix_to_word=None):
     return _RowsStage(net, [[int(w) for w in row if w != 0] for row in np.asarray(labels)], describe, expr_score, ix_to_word)
 
 
+def judge_stage(net, labels, gt_masks, gt_boxes, scale, judge, rerank, per_token, expr_score):
+    """the stage that judges every detection against the ground truth, or None without the options (rerank implies judging).
+    gt_masks / gt_boxes: eval_device._upload_image's device views.  ValueErrors name the options involved"""
+    if not judge and not rerank:
+        if per_token:
+            raise ValueError('per_token (--rerank_per_token) divides the re-ranking term: it needs rerank (--rerank)')
+        return None
+    n_tok = [int((np.asarray(row) != 0).sum()) + 1 for row in np.asarray(labels)]
+    return _JudgeStage(net, gt_masks, gt_boxes, scale, n_tok, rerank, per_token, bool(expr_score))
+
+
 def detect_image(net, data, labels, max_per_image=100, thresh=0.0, _cap=None, _pool_words=None, _capture=None, describe=False, expr_score=False,
-                 ix_to_word=None):
+                 ix_to_word=None, gt_masks=None, gt_boxes=None, rerank=None, per_token=False, selection=None):
     """data: {'data': float32 (1, H, W, 3) blob, 'im_info': [H, W, scale]} (+ 'file_name'); labels: int [S][T] token ids, zero padded.
     -> one list per sentence of dicts, class ascending and inside a class score descending: file_name, sent_index, roi (the proposal's
     row), category_id, box [x1, y1, x2, y2] (original image), score and (networks with a mask branch) area and segmentation
@@ -237,6 +351,12 @@ def detect_image(net, data, labels, max_per_image=100, thresh=0.0, _cap=None, _p
     ix_to_word ({str(id): word}), caption.  expr_score: also how well each detection's mask explains the sentence: expr_logprobs, the
     teacher-forced log-probabilities of the sentence's n tokens and the end token under that mask (n + 1 values), and expr_logprob, their
     sum.  Both run on the device behind each sentence (nets/caption_rows.py) and cost one more read-back per image.
+    gt_masks (uint8 [S][Hs][Ws]) with gt_boxes ([S][4], x1 y1 x2 y2 in the scaled image): every detection is judged against its sentence's
+    ground truth on the device (csrc/select.hip) and gains I, U (its mask's intersection and union with the gt mask, resized to the
+    canvas as the evaluation resizes it) and hit (its box's IoU with the gt box >= 0.5); `selection` (a list) receives per sentence
+    {file_name, sent_index, gt_area, rules}, where rules maps 'detector' (best score), 'oracle' (best mask IoU) and, with expr_score,
+    'speaker' (best expr_logprob) and 'rerank@<lambda>' for every lambda of `rerank` (best log(score) + lambda * expr_logprob, divided by
+    n + 1 with per_token) to {det (index in the sentence's list, -1 when it is empty), category_id, hit, I, U, key}.  One more read-back.
     (_cap, _pool_words: the buffers' first sizes instead of the defaults; _capture: a list that receives each sentence's head outputs and
     mask probabilities as device copies - checks.)"""
     labels = np.asarray(labels)
@@ -246,15 +366,25 @@ def detect_image(net, data, labels, max_per_image=100, thresh=0.0, _cap=None, _p
         raise ValueError('labels: every sentence needs at least one token')
     S = int(labels.shape[0])
     stage = rows_stage(net, labels, describe, expr_score, ix_to_word)
+    if (gt_masks is None) != (gt_boxes is None):
+        raise ValueError('gt_masks and gt_boxes come together')
+    if gt_masks is None and (rerank or per_token or selection is not None):
+        raise ValueError('rerank / per_token / selection judge the detections against a ground truth: they need gt_masks and gt_boxes')
     d = dict(data=data['data'], im_info=data['im_info'], labels=labels.astype(np.int64),
              gt_boxes=np.zeros((S, 5), np.float32), gt_masks=np.zeros((S, 1, 1), np.uint8))
+    if gt_masks is not None:
+        gm, gb = np.asarray(gt_masks), np.asarray(gt_boxes, dtype=np.float32)
+        if gm.ndim != 3 or gm.shape[0] != S or gb.ndim != 2 or gb.shape[0] != S or gb.shape[1] < 4:
+            raise ValueError('gt_masks is uint8 [S][Hs][Ws] and gt_boxes [S][4] with S = %d, got %s and %s' % (S, gm.shape, gb.shape))
+        d.update(gt_masks=gm, gt_boxes=gb)
     net.eval()
-    img, lab_d, lens, _, _ = ED._upload_image(net, d, S)
+    img, lab_d, lens, box_d, gm_d = ED._upload_image(net, d, S)
     im_info = np.asarray(data['im_info'], dtype=np.float32).reshape(-1)[:3]
     scale, ih, iw = ED._geometry(im_info)
+    judge = None if gt_masks is None else judge_stage(net, labels, gm_d, box_d, scale, True, rerank, per_token, expr_score)
     dd = dict(data=img, im_info=im_info, S=1)
     net.forward_test_image(dd)
-    det = _Detector(net, S, scale, ih, iw, max_per_image, thresh, _cap, _pool_words, _capture, stage)
+    det = _Detector(net, S, scale, ih, iw, max_per_image, thresh, _cap, _pool_words, _capture, stage, judge)
 
     def sentence(i):
         dd['labels'] = lab_d[i, :lens[i]]
@@ -262,4 +392,4 @@ def detect_image(net, data, labels, max_per_image=100, thresh=0.0, _cap=None, _p
         return net.forward_test_sentence(dd)
     for i in range(S):
         det.run(i, sentence(i))
-    return det.collect(data.get('file_name'), sentence)
+    return det.collect(data.get('file_name'), sentence, selection=selection)

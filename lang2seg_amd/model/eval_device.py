@@ -157,7 +157,13 @@ def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1, detect=
         from .detect_device import _Detector
         from .detect_device import rows_stage
         stage = rows_stage(net, np.asarray(data['labels'])[:n_sent], detect.get('describe'), detect.get('expr_score'), detect.get('ix_to_word'))
-        det = detect['detector'] = _Detector(net, n_sent, scale, ih, iw, detect.get('max_per_image', 100), detect.get('thresh', 0.0), stage=stage)
+        judge = None
+        if detect.get('judge') or detect.get('rerank') or detect.get('per_token'):
+            from .detect_device import judge_stage
+            judge = judge_stage(net, np.asarray(data['labels'])[:n_sent], gm, box_d, scale, detect.get('judge'), detect.get('rerank'),
+                                detect.get('per_token'), detect.get('expr_score'))
+        det = detect['detector'] = _Detector(net, n_sent, scale, ih, iw, detect.get('max_per_image', 100), detect.get('thresh', 0.0), stage=stage,
+                                             judge=judge)
         detect['sentence'] = sentence
     for i in range(n_sent):
         s = sentence(i)
@@ -206,10 +212,65 @@ class _Totals(object):
                 details.append((int(roi[j]), int(cls[j]), box[j].copy(), int(hit[j]), int(Is[j]), int(Us[j])))
 
 
+class _RuleTotals(object):
+    """_Totals' sums for one rule of the judge stage, fed from its choice records with _Totals.add's own expressions"""
+
+    def __init__(self):
+        self.acc, self.num_sent, self.cum_I, self.cum_U = 0, 0, 0, 0
+        self.seg_correct = np.zeros(len(EVAL_SEG_IOU_LIST), dtype=np.int32)
+
+    def add(self, choice):
+        if choice['hit']:
+            self.acc += 1
+        I, U = np.int64(choice['I']), np.int64(choice['U'])
+        self.cum_I += I; self.cum_U += U
+        with np.errstate(divide='ignore', invalid='ignore'):
+            for k, t in enumerate(EVAL_SEG_IOU_LIST):
+                self.seg_correct[k] += (I * 1.0 / U >= t)
+        self.num_sent += 1
+
+    def ints(self):
+        return [self.num_sent, self.acc, int(self.cum_I), int(self.cum_U)] + [int(c) for c in self.seg_correct]
+
+    def set_ints(self, v):
+        self.num_sent, self.acc, self.cum_I, self.cum_U = int(v[0]), int(v[1]), np.int64(v[2]), np.int64(v[3])
+        self.seg_correct = np.asarray(v[4:4 + len(EVAL_SEG_IOU_LIST)]).astype(np.int32)
+
+    def as_dict(self):
+        return dict(acc=self.acc, num_sent=self.num_sent, seg_correct=[int(c) for c in self.seg_correct], cum_I=int(self.cum_I),
+                    cum_U=int(self.cum_U))
+
+
+def check_judge_options(detections, judge, rerank, per_token, expr_score, variant=None):
+    """the ValueErrors of the judging options, each naming the options (and tool flags) involved, before anything runs -> the lambdas"""
+    from .detect_device import check_rerank
+    lambdas = check_rerank(rerank)
+    on = [n for n, v in (('judge (--judge_detections)', judge), ('rerank (--rerank)', lambdas), ('per_token (--rerank_per_token)', per_token)) if v]
+    if on and not detections:
+        raise ValueError('%s judge the detections: they need detections (--dump_detections)' % ', '.join(on))
+    if lambdas and not expr_score:
+        raise ValueError('rerank (--rerank) weighs the expression\'s log-likelihood: it needs expr_score (--expr_score 1)')
+    if per_token and not lambdas:
+        raise ValueError('per_token (--rerank_per_token) divides the re-ranking term: it needs rerank (--rerank)')
+    if on and variant == 'vgg':
+        raise ValueError('%s compare masks: --variant vgg has no mask branch' % ', '.join(on))
+    return lambdas
+
+
 def _run(loader, model, split, opt, rank, world, details, with_masks, progress, predictions=None, pool_words=None, detections=None,
-         describe=False, expr_score=False):
+         describe=False, expr_score=False, judge=False, rerank=None, per_token=False, selection=None, selection_totals=None):
     if (describe or expr_score) and detections is None:
         raise ValueError('describe / expr_score (--describe, --expr_score) add fields to the detections: they need detections (--dump_detections)')
+    lambdas = check_judge_options(detections is not None, judge, rerank, per_token, expr_score, None if with_masks else 'vgg')
+    judging = bool(judge or lambdas)
+    if (selection is not None or selection_totals is not None) and not judging:
+        raise ValueError('selection / selection_totals (--dump_selection) receive the judge stage\'s choices: they need judge (--judge_detections) '
+                         'or rerank (--rerank)')
+    rule_tot = {}
+    if judging:
+        from .detect_device import rule_names
+        rule_tot = {name: _RuleTotals() for name in rule_names(lambdas, expr_score)}      # (a dict keeps the rules' order)
+    sel = [] if judging and selection is None else selection
     num_sents = opt.get('num_sents', -1)
     verbose = opt.get('verbose', True)
     if world > 1 and num_sents > 0:
@@ -233,6 +294,8 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
             rec = O.eval_records(n, device)
             dopt = None if detections is None else dict(max_per_image=opt.get('max_per_image', 100), thresh=opt.get('det_thresh', 0.0),
                                                         describe=describe, expr_score=expr_score, ix_to_word=getattr(loader, 'ix_to_word', None))
+            if judging:
+                dopt.update(judge=True, rerank=lambdas, per_token=per_token)
             if dopt is None:
                 ex = _eval_image(model, data, n, rec, 0, with_masks, -1 if predictions is None else pool_words)
             else:
@@ -245,8 +308,13 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
                 chunks[-1] = rec_h
             if dopt is not None:                               # one read-back per image; a sentence that did not fit its buffers runs again
                 extra = dict(image_id=data['image_id']) if 'image_id' in data else None
-                for lst in dopt['detector'].collect(data.get('file_name'), dopt['sentence'], extra):
+                n_sel = len(sel) if judging else 0
+                for lst in dopt['detector'].collect(data.get('file_name'), dopt['sentence'], extra, selection=sel if judging else None):
                     detections.extend(lst)
+                if judging:
+                    for entry in sel[n_sel:]:
+                        for name, choice in entry['rules'].items():
+                            rule_tot[name].add(choice)
             if verbose:                                        # one host synchronisation per image, for the progress line
                 for r in chunks:
                     tot.add(r.cpu(), details, with_masks)
@@ -258,20 +326,27 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
         tot.add(torch.cat(chunks).cpu(), details, with_masks)  # the single read-back of the records
     if world > 1:
         import torch.distributed as dist
-        v = torch.tensor([tot.loss_evals, tot.acc, int(tot.cum_I), int(tot.cum_U)] + [int(c) for c in tot.seg_correct], dtype=torch.int64)
+        base = [tot.loss_evals, tot.acc, int(tot.cum_I), int(tot.cum_U)] + [int(c) for c in tot.seg_correct]
+        per_rule = [x for t in rule_tot.values() for x in t.ints()]                      # empty unless judging: the same one all_reduce
+        v = torch.tensor(base + per_rule, dtype=torch.int64)
         if dist.get_backend() != 'gloo':
             v = v.to(device)
         dist.all_reduce(v, op=dist.ReduceOp.SUM)
         v = v.cpu().numpy()
         tot.loss_evals = tot.num_sent = int(v[0]); tot.acc = int(v[1])
         tot.cum_I, tot.cum_U = np.int64(v[2]), np.int64(v[3])
-        tot.seg_correct = v[4:].astype(np.int32)
+        tot.seg_correct = v[4:len(base)].astype(np.int32)
         tot.seg_total = tot.loss_evals if with_masks else 0
+        w = 4 + len(EVAL_SEG_IOU_LIST)
+        for k, t in enumerate(rule_tot.values()):
+            t.set_ints(v[len(base) + k * w:len(base) + (k + 1) * w])
+    if selection_totals is not None:
+        selection_totals.update((name, t.as_dict()) for name, t in rule_tot.items())
     return tot
 
 
 def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=None, predictions=None, _pool_words=None, detections=None,
-                      describe=False, expr_score=False):
+                      describe=False, expr_score=False, judge=False, rerank=None, per_token=False, selection=None, selection_totals=None):
     """model/test.py eval_split on the device.  Returns its 7-tuple (acc, eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U,
     num_sent).  details: a list that receives (pred_roi, pred_class, pred_box, hit, I, U) per sentence of this rank.
     predictions: a list that receives one dict per sentence of this rank: file_name, sent_index (position in the image's test batch),
@@ -280,13 +355,19 @@ def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=
     opt['max_per_image'] (100) and opt['det_thresh'] (0.0) are its limits).  Metrics and predictions do not depend on it.
     describe / expr_score: detect_image's options for those detections (the captioner on every detection; the expression's log-likelihood
     under every detection's mask); they need `detections` and the cycle network.
+    judge / rerank (a list of lambdas; implies judge) / per_token: detect_image's judging of every detection against the sentence's ground
+    truth (I, U, hit per detection) and its rules; they need `detections`, rerank needs expr_score.  selection: a list that receives
+    per sentence of this rank {file_name, sent_index, gt_area, rules: {rule: {det, category_id, hit, I, U, key}}}; selection_totals: a dict
+    that receives per rule {acc, num_sent, seg_correct (at EVAL_SEG_IOU_LIST), cum_I, cum_U}, summed over the ranks.  Without them the
+    launches and every returned bit are what they are without these options.
     (_pool_words: the run-length pool of an image in words instead of its default budget; checks of the host fallback.)"""
     def progress(data, t):
         b = data['bounds']
         print('evaluating [%s] ... image[%d/%d]\'s sents, det acc=%.2f%%, seg acc=%.2f%%, seg IoU=%.2f%%' % (
             split, b['it_pos_now'], b['it_max'], t.acc * 100.0 / max(t.loss_evals, 1), t.seg_correct[0] * 100.0 / max(t.seg_total, 1),
             t.cum_I * 100.0 / max(t.cum_U, 1)))
-    t = _run(loader, model, split, opt, rank, world, details, True, progress, predictions, _pool_words, detections, describe, expr_score)
+    t = _run(loader, model, split, opt, rank, world, details, True, progress, predictions, _pool_words, detections, describe, expr_score,
+             judge, rerank, per_token, selection, selection_totals)
     return t.acc / t.loss_evals, EVAL_SEG_IOU_LIST, t.seg_correct, t.seg_total, t.cum_I, t.cum_U, t.num_sent
 
 

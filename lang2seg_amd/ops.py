@@ -764,6 +764,65 @@ def detect_paste(mask_prob, rec, count, ih, iw, canvases):
     call('l2s_detect_paste', ptr(mask_prob), ms, ptr(rec), ptr(count), cap, ih, iw, ptr(canvases), stream())
 
 
+# ------------------------------------------------------------------ judging the detections (csrc/select.hip)
+DET_GT_BYTES = 16          # l2s_det_gt: I, U, hit, reserved (int32)
+DET_CHOICE_BYTES = 40      # l2s_det_choice: det, cls, hit, reserved (int32), I, U (int64), key (float64)
+DET_MAX_LAMBDA = 8
+_DET_GT = [('I', '<i4'), ('U', '<i4'), ('hit', '<i4'), ('reserved', '<i4')]
+_DET_CHOICE = [('det', '<i4'), ('cls', '<i4'), ('hit', '<i4'), ('reserved', '<i4'), ('I', '<i8'), ('U', '<i8'), ('key', '<f8')]
+
+
+def _records(rec, fields, nbytes):
+    import numpy as np
+    a = rec.numpy() if isinstance(rec, torch.Tensor) else np.asarray(rec)
+    a = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    if a.size % nbytes:
+        raise ValueError('%d bytes are no whole number of %d-byte records' % (a.size, nbytes))
+    return a.view(np.dtype(fields))
+
+
+def det_gt_fields(rec):
+    """host l2s_det_gt rows (any integer array of n * 16 bytes) -> (I, U, hit) numpy int32 arrays"""
+    a = _records(rec, _DET_GT, DET_GT_BYTES)
+    return a['I'], a['U'], a['hit']
+
+
+def det_choice_fields(rec):
+    """host l2s_det_choice rows (any integer array of n * 40 bytes) -> (det, cls, hit, I, U, key): int32 x 3, int64 x 2, float64"""
+    a = _records(rec, _DET_CHOICE, DET_CHOICE_BYTES)
+    return a['det'], a['cls'], a['hit'], a['I'], a['U'], a['key']
+
+
+def detect_gt_iou(canvases, rec, count, gt, gt_box, im_scale, out, gt_area, clear=True):
+    """every detection d < count[0] of canvases uint8 [cap][ih][iw] against the gt mask uint8 [Hs][Ws] (PIL NEAREST resized to the canvas)
+    and the gt box f32 [4] (scaled image): out int32 [cap][4] (l2s_det_gt: I, U, hit), gt_area int32 [1].  The kernel accumulates:
+    clear=False only for outputs that are zero already"""
+    cap, ih, iw = canvases.shape
+    if rec.numel() * rec.element_size() < cap * DET_RECORD_BYTES or out.numel() * out.element_size() < cap * DET_GT_BYTES or gt_area.numel() < 1:
+        raise ValueError('detect_gt_iou: records or outputs smaller than cap = %d' % cap)
+    if gt.dim() != 2 or gt.dtype != torch.uint8 or not gt.is_contiguous() or gt_box.numel() < 4:
+        raise ValueError('detect_gt_iou: gt is a contiguous uint8 [Hs][Ws] mask and gt_box 4 floats, got %s %s' % (tuple(gt.shape), gt.dtype))
+    if clear:
+        memset_zero(out)
+        memset_zero(gt_area)
+    call('l2s_detect_gt_iou', ptr(canvases), ptr(rec), ptr(count), cap, ih, iw, ptr(gt), gt.shape[0], gt.shape[1], ptr(gt_box), float(im_scale),
+         ptr(out), ptr(gt_area), stream())
+
+
+def detect_choose(rec, gt_rows, count, cap, gt_area, out, expr=None, lambdas=(), per_token=False, n_tok=1):
+    """one detection per rule: out (2 + (1 + len(lambdas) if expr is given) l2s_det_choice records of 40 bytes, 8-byte aligned) =
+    detector, oracle[, speaker, rerank@lambda ...]; expr: device f32 [cap] (caption_score_rows' score)"""
+    lam = [float(v) for v in lambdas]
+    n_rules = 2 + (1 + len(lam) if expr is not None else 0)
+    if out.numel() * out.element_size() < n_rules * DET_CHOICE_BYTES or out.data_ptr() % 8:
+        raise ValueError('detect_choose: %d choice records need %d bytes, 8-byte aligned' % (n_rules, n_rules * DET_CHOICE_BYTES))
+    if expr is not None and (expr.dtype != torch.float32 or expr.numel() < cap):
+        raise ValueError('detect_choose: expr is float32 [cap = %d]' % cap)
+    arr = (C.c_float * max(len(lam), 1))(*lam)
+    call('l2s_detect_choose', ptr(rec), ptr(gt_rows), ptr(count), cap, ptr(gt_area), ptr(expr), arr, len(lam), 1 if per_token else 0, int(n_tok),
+         ptr(out), stream())
+
+
 # ------------------------------------------------------------------ caption decoding (csrc/decode.hip)
 BEAM_MAX, BEAM_MAX_T = 16, 64
 

@@ -3,7 +3,8 @@
 the batched paste and the batched run-length encoder) on the heads' outputs of one sentence of the full-size ResNet-101 'cycle' network
 (initial weights, bf16, a 600 x 1000 SyntheticLoader image: post = 300, C = 81, canvas 375 x 625), by HIP events, stage by stage; next to
 the host restatement of NMS + select on the same outputs (tests/detect_util.py: numpy, including the D2H of the three matrices; it has
-no mask stage, so it is a lower bound of a host path).  Prints one JSON line."""
+no mask stage, so it is a lower bound of a host path).  --judge 1: also the judge stage behind it (l2s_detect_gt_iou, l2s_detect_choose)
+and the bytes per second l2s_detect_gt_iou achieves on the detections' boxes.  Prints one JSON line."""
 import argparse
 import json
 import os.path as osp
@@ -26,6 +27,7 @@ def main():
     ap.add_argument('--dtype', default='bf16'); ap.add_argument('--max_per_image', type=int, default=100)
     ap.add_argument('--thresh', type=float, default=0.0); ap.add_argument('--iters', type=int, default=50)
     ap.add_argument('--out', default=None, help='also write the JSON result to this file')
+    ap.add_argument('--judge', type=int, default=0, help='1: also time the judge stage (l2s_detect_gt_iou, l2s_detect_choose) behind the sentence')
     a = ap.parse_args()
     import detect_util as DU
     from lang2seg_amd import ops as O
@@ -46,7 +48,7 @@ def main():
     net = resnetv1(opt, batch_size=1, num_layers=101, variant='cycle')
     net.create_architecture(81, tag='default', anchor_scales=cfg.ANCHOR_SCALES, anchor_ratios=cfg.ANCHOR_RATIOS)
     net.eval()
-    img, lab_d, lens, _, _ = ED._upload_image(net, b, 1)
+    img, lab_d, lens, box_d, gm = ED._upload_image(net, b, 1)
     im_info = np.asarray(b['im_info'], dtype=np.float32).reshape(-1)[:3]
     scale, ih, iw = ED._geometry(im_info)
     d = dict(data=img, im_info=im_info, S=1, labels=lab_d[0, :lens[0]], T=lens[0])
@@ -98,6 +100,38 @@ def main():
     res['host_nms_select_us'] = host[len(host) // 2][0] * 1e6
     res['host_d2h_us'] = host[len(host) // 2][1] * 1e6
     res['host_detections'] = int(y[0].size)
+    if a.judge:
+        # the judge stage behind the same sentence (model/detect_device.py _JudgeStage): its two launches on the canvases and records the
+        # detection stage left, with a synthetic expression score (the captioner is the rows stage's time, not this one's)
+        stage = DD._JudgeStage(net, gm[:1], box_d[:1], scale, [lens[0] + 1], rerank=[0.0, 0.5, 4.0], with_expr=True)
+        arr = stage.alloc(1, cap)
+        choice, rows, area = stage._views(arr, 0, cap)
+        expr = torch.from_numpy(-np.random.RandomState(0).rand(cap).astype(np.float32) * 30).cuda()
+        cnt = out['count'][0:1]
+
+        def judge():
+            O.memset_zero(arr)
+            stage.run(0, arr, out['canvases'], out['rec'], cnt, cap, expr)
+        t_zero = _event_us(lambda: O.memset_zero(arr), a.iters)
+        res['judge_stage_us'] = _event_us(judge, a.iters) - t_zero
+        res['judge_zero_us'] = t_zero                               # (in the product the image's array is zeroed once, at its allocation)
+
+        def gt_iou():
+            O.memset_zero(arr)
+            O.detect_gt_iou(out['canvases'], out['rec'], cnt, gm[0], box_d[0], scale, rows, area, clear=False)
+        res['gt_iou_us'] = _event_us(gt_iou, a.iters) - t_zero
+        res['choose_us'] = _event_us(lambda: O.detect_choose(out['rec'], rows, cnt, cap, area, choice, expr, stage.lambdas, False, lens[0] + 1), a.iters)
+        # what l2s_detect_gt_iou streams: every detection's box of its canvas, and the resized gt once (its gathers under set pixels hit
+        # the cache); the canvases as a whole are written * ih * iw bytes
+        _, _, box, _, _ = O.det_record_fields(out['rec'].cpu())
+        f = np.float32
+        bx = np.clip(box[:written], 0, [f(iw - 1), f(ih - 1), f(iw - 1), f(ih - 1)]).astype(f)
+        bw, bh = (bx[:, 2] - bx[:, 0] + f(1)).astype(np.int64), (bx[:, 3] - bx[:, 1] + f(1)).astype(np.int64)
+        res['gt_iou_box_bytes'] = int((bw * bh).sum())
+        res['gt_iou_gt_bytes'] = int(ih * iw)
+        res['gt_iou_whole_canvas_bytes'] = int(written * ih * iw)
+        res['gt_iou_GBps'] = (res['gt_iou_box_bytes'] + res['gt_iou_gt_bytes']) / (res['gt_iou_us'] * 1e-6) / 1e9
+        res['judge_rules'] = stage.names
     if a.out:
         with open(a.out, 'w') as f:
             json.dump(res, f, indent=1)

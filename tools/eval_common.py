@@ -36,6 +36,14 @@ def parse_args(argv=None):
                    'detection (caption_tokens, caption_logprobs, caption; greedy)')
     p.add_argument('--expr_score', type=int, default=0, help='--dump_detections on the cycle network: also the log-likelihood of the sentence '
                    'under every detection\'s mask (expr_logprob, expr_logprobs)')
+    p.add_argument('--judge_detections', type=int, default=0, help='--dump_detections on a network with masks: also judge every detection against '
+                   'the sentence\'s ground truth on the device (I, U, hit per detection) and print what the rules detector / oracle would score')
+    p.add_argument('--rerank', default=None, help='--dump_detections --expr_score 1: lambdas L1,L2,... (at most 8); per lambda the rule that picks '
+                   'the detection with the best log(score) + lambda * expr_logprob, and the rule speaker (best expr_logprob); implies '
+                   '--judge_detections 1')
+    p.add_argument('--rerank_per_token', type=int, default=0, help='--rerank: divide expr_logprob by the expression\'s tokens + 1')
+    p.add_argument('--dump_selection', default=None, help='with judging: write every sentence\'s choice per rule as one JSON list to this path '
+                   '(rank suffix as above)')
     # the expression encoder the snapshot was trained with (tools/opt.py; a snapshot of another encoder is an error that names the flag)
     # (default None: tools/opt.py's own defaults apply)
     p.add_argument('--rnn_type', default=None, help='lstm, gru or rnn'); p.add_argument('--rnn_num_layers', type=int, default=None)
@@ -52,6 +60,48 @@ def dump_predictions(args, preds, rank, world, key='dump_predictions', what='pre
     with open(path, 'w') as f:
         json.dump(preds, f)
     print('wrote %d %s to %s' % (len(preds), what, path))
+
+
+def parse_rerank(text):
+    """--rerank L1,L2,... -> the list of floats (None without the flag).  ValueError naming --rerank on an entry that is no finite float
+    and on more than 8 entries"""
+    if text is None or text == '':
+        return None
+    out = []
+    for part in str(text).split(','):
+        try:
+            out.append(float(part))
+        except ValueError:
+            raise ValueError('--rerank: every entry of L1,L2,... is a finite float, got %r' % part)
+    from lang2seg_amd.model.detect_device import check_rerank
+    return check_rerank(out)
+
+
+def selection_options(args, variant):
+    """the judging flags -> (judge, the lambdas or None, per_token).  ValueErrors name the flags involved"""
+    lambdas = parse_rerank(args.get('rerank'))
+    judge = bool(args.get('judge_detections')) or bool(lambdas)
+    flags = [f for f, v in (('--judge_detections', args.get('judge_detections')), ('--rerank', lambdas),
+                            ('--rerank_per_token', args.get('rerank_per_token')), ('--dump_selection', args.get('dump_selection'))) if v]
+    if flags and not args.get('dump_detections'):
+        raise ValueError('%s judge the detections: they need --dump_detections PATH' % ', '.join(flags))
+    if lambdas and not args.get('expr_score'):
+        raise ValueError('--rerank weighs the expression\'s log-likelihood under every detection\'s mask: it needs --expr_score 1')
+    if args.get('rerank_per_token') and not lambdas:
+        raise ValueError('--rerank_per_token divides the re-ranking term: it needs --rerank L1,L2,...')
+    if args.get('dump_selection') and not judge:
+        raise ValueError('--dump_selection writes the judged choices: it needs --judge_detections 1 or --rerank L1,L2,...')
+    if flags and variant == 'vgg':
+        raise ValueError('%s compare masks: --variant vgg has no mask branch' % ', '.join(flags))
+    return judge, lambdas, bool(args.get('rerank_per_token'))
+
+
+def print_selection(totals):
+    """one line per rule: det acc, seg acc at 0.5 and overall IoU of the detection that rule picks"""
+    for name, t in totals.items():
+        n = max(t['num_sent'], 1)
+        print('rule %-14s det acc %.2f%%, seg acc@0.5 %.2f%%, overall IoU %.2f%% (%d sents)' % (
+            name, t['acc'] * 100.0 / n, t['seg_correct'][0] * 100.0 / n, t['cum_I'] * 100.0 / max(t['cum_U'], 1), t['num_sent']))
 
 
 def main(args, variant):
@@ -73,6 +123,7 @@ def main(args, variant):
             raise ValueError('--%s 1 needs --dump_detections PATH: it adds fields to every detection (--%s, --dump_detections)' % (k, k))
     if (args.get('describe') or args.get('expr_score')) and variant == 'vgg':
         raise ValueError('--describe / --expr_score: --variant vgg has no caption branch (the cycle network has one)')
+    judge, lambdas, per_token = selection_options(args, variant)
     preds = [] if args.get('dump_predictions') else None
     dets = [] if args.get('dump_detections') else None
     torch.cuda.set_device(local % max(torch.cuda.device_count(), 1))
@@ -135,10 +186,14 @@ def main(args, variant):
                 det_thresh=args.get('det_thresh', 0.0))
     if args['device_eval']:
         from lang2seg_amd.model.eval_device import eval_split_device
+        sel, sel_tot = ([], {}) if judge else (None, None)
+        kw = dict(judge=True, rerank=lambdas, per_token=per_token, selection=sel, selection_totals=sel_tot) if judge else {}
         res = eval_split_device(loader, net, None, split, eopt, rank=rank, world=world, predictions=preds, detections=dets,
-                                describe=bool(args.get('describe')), expr_score=bool(args.get('expr_score')))
+                                describe=bool(args.get('describe')), expr_score=bool(args.get('expr_score')), **kw)
         dump_predictions(args, preds, rank, world)
         dump_predictions(args, dets, rank, world, 'dump_detections', 'detections')
+        if args.get('dump_selection'):
+            dump_predictions(args, sel, rank, world, 'dump_selection', 'selections')
     else:
         res = eval_split(loader, net, None, split, eopt)
     acc, eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U, num_sent = res
@@ -148,6 +203,8 @@ def main(args, variant):
     results_str, prec, iou = summarize(eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U)
     print('Segmentation results on [%s][%s]' % (opt['dataset_splitBy'], split))
     print(results_str)
+    if args['device_eval'] and judge:
+        print_selection(sel_tot)
     # tools/eval_spatial.py:95-98,121-124: the two running result logs
     res_dir = args.get('results_dir') or osp.join(ROOT, 'experiments')
     os.makedirs(res_dir, exist_ok=True)
