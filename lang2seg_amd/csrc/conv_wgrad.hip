@@ -27,20 +27,15 @@
 //   * l2s_conv_wgrad (one problem per launch) remains for callers outside a step; with a workspace it may split the pixels:
 //     every workgroup then stores its partial tile into its own slab and a second launch adds the slabs to dW in a fixed
 //     order (still no floating-point atomics).
-#include "common.h"
-#include "../../include/lang2seg_hip.h"
-#include "wgrad_internal.h"
+#include "wgrad_common.h"
 #include <stdlib.h>
 
 namespace {
-
-constexpr unsigned OOR = 0x80000000u;
+using namespace l2s_wgrad;
 
 template <typename T> struct WGT;
 template <> struct WGT<bf16_t> { static constexpr int BKP = 32; static constexpr int PADB = 32; };   // row skew 8 dwords: tr reads conflict-free
 template <> struct WGT<float> { static constexpr int BKP = 16; static constexpr int PADB = 64; };
-
-typedef l2s_wgrad_prob wgp;
 
 // One output tile (co tile, ci tile, tap or filter row) of problem p over the slices [s_begin, s_end) of segment `seg`'s pixels
 // (s_end < 0: all slices of every segment).  out: where the tile goes (dW, or a split-K slab); accumulate: out += tile.
@@ -89,22 +84,12 @@ __device__ __forceinline__ void wgrad_tile(const wgp& p, int co0, int ci0, int t
         const int trow = trow0 + h * 32;
         uint4 fa[TM];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          const char* q = a + trow * LRA + (wm * WM + i * 16) * 2 + tcol;
-          s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(q));
-          s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(q + 16 * LRA));
-          fa[i] = __builtin_bit_cast(uint4, (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
-        }
+        for (int i = 0; i < TM; ++i) fa[i] = lds_frag(a + trow * LRA + (wm * WM + i * 16) * 2 + tcol, LRA);
 #pragma unroll
         for (int t = 0; t < TX; ++t) {
           uint4 fb[TN];
 #pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const char* q = b + (trow + t) * LRB + (wn * WN + j * 16) * 2 + tcol;
-            s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(q));
-            s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(q + 16 * LRB));
-            fb[j] = __builtin_bit_cast(uint4, (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
-          }
+          for (int j = 0; j < TN; ++j) fb[j] = lds_frag(b + (trow + t) * LRB + (wn * WN + j * 16) * 2 + tcol, LRB);
 #pragma unroll
           for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -140,7 +125,8 @@ __device__ __forceinline__ void wgrad_tile(const wgp& p, int co0, int ci0, int t
     const int Wv = OW + (TX == 3 ? 1 : 0);               // virtual row width (with the zero column)
     const int ohwv = OH * Wv;
     const int Mv = n_img * ohwv;
-    const int sa = BKP / ohwv, sb = (BKP - sa * ohwv) / Wv, sc = BKP - sa * ohwv - sb * Wv;   // BKP = sa*OH*Wv + sb*Wv + sc
+    int sa, sb, sc;
+    slice_step(BKP, ohwv, Wv, sa, sb, sc);               // BKP = sa*OH*Wv + sb*Wv + sc
     const int nslices = (Mv + BKP - 1) / BKP;
     const int per = (nslices + nsplit - 1) / nsplit;
     const int s_begin = split_idx * per;
@@ -161,16 +147,9 @@ __device__ __forceinline__ void wgrad_tile(const wgp& p, int co0, int ci0, int t
 #pragma unroll
     for (int j = 0; j < NVB; ++j) bcok[j] = (ci0 + (lq * NVB + j) * VE) < p.Cin;
     const unsigned acol = (unsigned)((co0 + lq * NVA * VE) * ES), bcol = (unsigned)((ci0 + lq * NVB * VE) * ES);
-    {
-      const int pix = pb0 + lrow;
-      an = pix / ohwv; const int rem = pix - an * ohwv; ay = rem / Wv; ax = rem - ay * Wv;
-    }
-    auto place = [&](int pix, int& n, int& y, int& x) {            // TX == 3: image row r holds virtual pixel base - 1 + r
-      if (pix < 0) { n = 0; y = 0; x = -1; }
-      else { n = pix / ohwv; const int rem = pix - n * ohwv; y = rem / Wv; x = rem - y * Wv; }
-    };
-    place(pb0 + lrow - (TX == 3 ? 1 : 0), bn, by, bx);
-    if (TX == 3) place(pb0 + BKP + lrow - 1, tn, ty, tx);           // (only used by the `tail` threads: lrow is 0 or 1 there)
+    pixel_split(pb0 + lrow, ohwv, Wv, an, ay, ax);
+    pixel_place(pb0 + lrow - (TX == 3 ? 1 : 0), ohwv, Wv, bn, by, bx);           // TX == 3: image row r holds virtual pixel base - 1 + r
+    if (TX == 3) pixel_place(pb0 + BKP + lrow - 1, ohwv, Wv, tn, ty, tx);        // (only used by the `tail` threads: lrow is 0 or 1 there)
     auto advance = [&](int& n, int& y, int& x) {
       x += sc; if (x >= Wv) { x -= Wv; ++y; }
       y += sb; if (y >= OH) { y -= OH; ++n; }
@@ -263,12 +242,7 @@ __device__ __forceinline__ void wgrad_tile(const wgp& p, int co0, int ci0, int t
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const int ci = ci0 + wn * WN + j * 16 + fg * 4;
-        if (co < p.Cout && ci < p.Cin) {                 // Cin % 4 == 0
-          float4* q = (float4*)(out + (long)co * Kw + (long)tap * p.Cin + ci);
-          float4 v = make_float4(acc[t][i][j][0], acc[t][i][j][1], acc[t][i][j][2], acc[t][i][j][3]);
-          if (accumulate) { const float4 o = *q; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
-          *q = v;
-        }
+        if (co < p.Cout && ci < p.Cin) dw_store((float4*)(out + (long)co * Kw + (long)tap * p.Cin + ci), f4(acc[t][i][j]), accumulate);   // Cin % 4 == 0
       }
     }
   }
@@ -289,26 +263,18 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const wgp p, int cblocks, fl
 
 
 // ---- a whole backward stage per launch: problems in a device table, workgroup -> (problem, tile) through the tile prefix ----
-struct wg_prefix { int n; int tile0[L2S_WGRAD_MAX_GROUP + 1]; };
+typedef l2s::wgrad_tile_prefix wg_prefix;
 
 template <typename T, int BM, int BN, int TX, int D, int KSTEP, int WGM = 2, int WGN = 2>
 __global__ __launch_bounds__(64 * WGM * WGN) void wgrad_grouped_kernel(const wgp* __restrict__ tab, const wg_prefix pre, float* ws) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // XCD-aware order: workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8), each with its own L2; XCD x takes the x-th
-  // CONTIGUOUS eighth of the tile list, whose neighbours share the X tile (same ci tile and tap, consecutive co tiles / pixel ranges),
-  // instead of every XCD fetching every operand tile.  The grid may be smaller than the tile list (l2s_wgrad_grid_cap): a workgroup
-  // then walks tiles L, L + gridDim.x, ... (gridDim.x a multiple of 8 keeps a workgroup on its XCD's eighth).
+  // XCD-aware order (tile_of): the neighbours in the tile list share the X tile (same ci tile and tap, consecutive co tiles / pixel ranges).
+  // The grid may be smaller than the tile list (l2s_wgrad_grid_cap): a workgroup then walks tiles L, L + gridDim.x, ... (gridDim.x a
+  // multiple of 8 keeps a workgroup on its XCD's eighth).
   const int G = pre.tile0[pre.n];
   for (int L = blockIdx.x; L < G; L += gridDim.x) {
-    int bid;
-    {
-      const int x = L & 7, slot = L >> 3, q = G >> 3, r = G & 7;
-      bid = x * q + min(x, r) + slot;
-    }
-    int lo = 0, hi = pre.n;                                // tile0[lo] <= bid < tile0[hi]
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (pre.tile0[mid] <= bid) lo = mid; else hi = mid; }
-    const wgp p = tab[lo];                                 // uniform: scalar loads
-    int t = bid - pre.tile0[lo];
+    int t;
+    const wgp p = tab[tile_of(pre, L, t)];                 // uniform: scalar loads
     const int co_tiles = (p.Cout + BM - 1) / BM, ci_tiles = (p.Cin + BN - 1) / BN;
     const int split = p.split > 1 ? p.split : 1;
     // split index fastest, then co: consecutive workgroups (dealt round-robin over the XCDs) share the X tile and the tap
@@ -320,43 +286,34 @@ __global__ __launch_bounds__(64 * WGM * WGN) void wgrad_grouped_kernel(const wgp
   }
 }
 
-// problems of a grouped launch whose pixels were split: dW[e] += slab_0[e] + slab_1[e] + ... (fixed order); grid (blocks, problems)
-__global__ __launch_bounds__(256) void wgrad_reduce_grouped_kernel(const wgp* __restrict__ tab, const float* __restrict__ ws) {
-  const wgp p = tab[blockIdx.y];
-  if (p.split <= 1) return;
-  const long slab = (long)p.Cout * p.KH * p.KW * p.Cin, n4 = slab / 4;
-  const float* w0 = ws + p.ws_off;
+// dW[e] (+)= slab_0[e] + slab_1[e] + ... in that order (a fixed summation tree: bit-reproducible); slab k at ws + k * slab, n4 float4 each
+__device__ __forceinline__ void reduce_slabs(float* dw, const float* ws, long n4, long slab, int split, bool accumulate) {
   for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n4; e += (long)gridDim.x * blockDim.x) {
-    float4 s = ((const float4*)w0)[e];
-    for (int k = 1; k < p.split; ++k) {
-      const float4 v = ((const float4*)(w0 + (long)k * slab))[e];
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    if (!(p.flags & 1)) { const float4 o = ((float4*)p.dw)[e]; s.x += o.x; s.y += o.y; s.z += o.z; s.w += o.w; }
-    ((float4*)p.dw)[e] = s;
+    float4 s = ((const float4*)ws)[e];
+    for (int k = 1; k < split; ++k) s = add4(s, ((const float4*)(ws + (long)k * slab))[e]);
+    dw_store((float4*)dw + e, s, accumulate);
   }
 }
 
-// dW[e] += slab_0[e] + slab_1[e] + ... in that order (a fixed summation tree: bit-reproducible)
+// problems of a grouped launch whose pixels were split; grid (blocks, problems)
+__global__ __launch_bounds__(256) void wgrad_reduce_grouped_kernel(const wgp* __restrict__ tab, const float* __restrict__ ws) {
+  const wgp p = tab[blockIdx.y];
+  if (p.split <= 1) return;
+  const long slab = (long)p.Cout * p.KH * p.KW * p.Cin;
+  reduce_slabs(p.dw, ws + p.ws_off, slab / 4, slab, p.split, !(p.flags & 1));
+}
+
+// one problem whose pixels were split (l2s_conv_wgrad)
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(float* __restrict__ dw, const float* __restrict__ ws, long n4, long slab, int split) {
-  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n4; e += (long)gridDim.x * blockDim.x) {
-    float4 s = ((const float4*)ws)[e];
-    for (int k = 1; k < split; ++k) {
-      const float4 v = ((const float4*)(ws + (long)k * slab))[e];
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    float4 o = ((float4*)dw)[e];
-    o.x += s.x; o.y += s.y; o.z += s.z; o.w += s.w;
-    ((float4*)dw)[e] = o;
-  }
+  reduce_slabs(dw, ws, n4, slab, split, true);
 }
 
 // ---- variants (tile, taps per workgroup): 0 = 64x64 per tap, 1 = 128x128 per tap, 2 = 64x64 filter row, 3 = 128(co)x64 filter row,
 // 4 = 256x256 per tap with 8 waves, 5 = the LDS-DMA 128x128 filter-row tile with stream-K balancing (conv_wgrad_dma.hip)
 // (4 and 5: bf16 grouped launches only; `tile` = 256 allows them) ----
 // The choices below are constants of the product build (csrc/knobs.h):
-//  * wgrad_row3_dma_wgs = 128: the stream-K launch of the LDS-DMA filter-row tile takes half the CUs (a workgroup owns its CU - 132 KB of LDS, 240 VGPRs
-//    x 8 waves - and the other queues' launches need somewhere to run: 96 / 128 / 160 / 256 -> 190.1 / 189.1 / 189.0 / 185.5 img/s, same box x 3)
+//  * wgrad_row3_dma_wgs: the stream-K launch of the LDS-DMA filter-row tile takes part of the CUs (a workgroup owns its CU - 132 KB of LDS, 240 VGPRs
+//    x 8 waves - and the other queues' launches need somewhere to run); the number and its measurements are in knobs.h
 //  * wgrad_1x1_dma = 0: the LDS-DMA 256x256 tile of conv_wgrad_dma1.hip (variant 6) for the large 1x1 problems is built, tested, and no faster:
 //    447-455 against 425-431 us alone on 120 CUs, 206.9 against 208.4 img/s in the step; both tiles move 32 KB per slice and CU in ~0.95 us
 //  * wgrad_row3_wide = 1: 512+ channels on both sides (RPN's 3x3 on the map) take the filter-row tile from any pixel count (its stream-K launch needs no pixel split)
@@ -369,6 +326,9 @@ int variant_of(int Cin, int Cout, int KH, int KW, int stride, int pad, int same_
   if (wgrad_1x1_dma && tile == 256 && big && KH * KW == 1 && stride == 1 && pad == 0 && same_hw && Cout % 256 == 0 && Cin % 256 == 0) return 6;
   if (tile == 256 && big && KH * KW == 1 && Cout % 256 == 0 && Cin % 256 == 0) return 4;
   return (tile == 128 || ((!tile || tile == 256) && big && KH * KW == 1)) ? 1 : 0;
+}
+int variant_of(const l2s_wgrad_desc& d) {
+  return variant_of(d.Cin, d.Cout, d.KH, d.KW, d.stride, d.pad, d.OH == d.IH && d.OW == d.IW, (long)d.n_img * d.OH * d.OW, d.tile);
 }
 void variant_tile(int v, int& bm, int& bn, int& tx) {
   if (v == 4 || v == 6) { bm = 256; bn = 256; tx = 1; return; }
@@ -416,15 +376,13 @@ int launch_grouped(const wgp* tab, const wg_prefix& pre, float* ws, bool any_spl
   constexpr size_t want = 54000, want_big = 83000;
   if (BM * BN >= 128 * 128) { if (want_big > lds) lds = want_big; }
   else if (want > lds) lds = want;
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)wgrad_grouped_kernel<T, BM, BN, TX, D, KSTEP, WGM, WGN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
   int grid = pre.tile0[pre.n];
   {
     const int cap = l2s_knobs::wgrad_grid_cap & 0xffff, vmask = l2s_knobs::wgrad_grid_cap >> 16;      // (tools build: cap | variant mask << 16; mask 0 = every variant)
     const int var = BM == 256 ? 4 : (TX == 3 ? (BM == 128 ? 3 : 2) : (BM == 128 ? 1 : 0));
     if (cap > 0 && grid > cap && (vmask == 0 || ((vmask >> var) & 1))) grid = cap;
   }
-  L2S_LAUNCH((wgrad_grouped_kernel<T, BM, BN, TX, D, KSTEP, WGM, WGN>), dim3(grid), dim3(64 * WGM * WGN), lds, st, tab, pre, ws);
+  WGRAD_LAUNCH((wgrad_grouped_kernel<T, BM, BN, TX, D, KSTEP, WGM, WGN>), dim3(grid), dim3(64 * WGM * WGN), lds, st, tab, pre, ws);
   if (any_split) {
     const float* wsc = ws;
     L2S_LAUNCH(wgrad_reduce_grouped_kernel, dim3(64, pre.n), dim3(256), 0, st, tab, wsc);
@@ -456,36 +414,22 @@ extern "C" long l2s_wgrad_tiles(int variant, int Cin, int Cout, int KH, int KW) 
 extern "C" int l2s_conv_wgrad_grouped(const l2s_wgrad_prob* table_dev, const l2s_wgrad_prob* table_host, int nprob, int variant, int dtype,
                                       float* ws, size_t ws_bytes, hipStream_t stream) {
   if (!table_dev || !table_host || nprob < 1 || nprob > L2S_WGRAD_MAX_GROUP || variant < 0 || variant > 6) return L2S_EINVAL;
-  if (variant == 6) {
-    if (dtype != L2S_BF16) return L2S_EINVAL;
-    for (int i = 0; i < nprob; ++i) if (!prob_ok(table_host[i], dtype) || !table_host[i].dw) return L2S_EINVAL;
-    return l2s::wgrad_1x1_dma_launch(table_dev, table_host, nprob, stream);
-  }
-  if (variant == 5) {
-    if (dtype != L2S_BF16) return L2S_EINVAL;
-    for (int i = 0; i < nprob; ++i) if (!prob_ok(table_host[i], dtype) || !table_host[i].dw) return L2S_EINVAL;
-    return l2s::wgrad_row3_dma_launch(table_dev, table_host, nprob, ws, ws_bytes, l2s_knobs::wgrad_row3_dma_wgs, stream);
-  }
-  wg_prefix pre;
-  pre.n = nprob;
-  long t = 0;
+  if (variant >= 5 && dtype != L2S_BF16) return L2S_EINVAL;
+  for (int i = 0; i < nprob; ++i) if (!prob_ok(table_host[i], dtype) || !table_host[i].dw) return L2S_EINVAL;
+  if (variant == 6) return l2s::wgrad_1x1_dma_launch(table_dev, table_host, nprob, stream);
+  if (variant == 5) return l2s::wgrad_row3_dma_launch(table_dev, table_host, nprob, ws, ws_bytes, l2s_knobs::wgrad_row3_dma_wgs, stream);
   bool any_split = false;
   for (int i = 0; i < nprob; ++i) {
     const wgp& q = table_host[i];
-    if (!prob_ok(q, dtype) || !q.dw) return L2S_EINVAL;
     if ((variant == 2 || variant == 3) && !(q.KH == 3 && q.KW == 3 && q.stride == 1 && q.pad == 1)) return L2S_EINVAL;
-    const int split = q.split > 1 ? q.split : 1;
-    if (split > 1) {
+    if (q.split > 1) {
       const long slab = (long)q.Cout * q.KH * q.KW * q.Cin;
-      if (!ws || q.ws_off < 0 || (q.ws_off % 4) || (size_t)(q.ws_off + split * slab) * 4 > ws_bytes) return L2S_EINVAL;
+      if (!ws || q.ws_off < 0 || (q.ws_off % 4) || (size_t)(q.ws_off + q.split * slab) * 4 > ws_bytes) return L2S_EINVAL;
       any_split = true;
     }
-    pre.tile0[i] = (int)t;
-    t += variant_tiles(variant, q.Cin, q.Cout, q.KH, q.KW) * split;
   }
-  if (t >= (1L << 30)) return L2S_EINVAL;
-  pre.tile0[nprob] = (int)t;
-  for (int i = nprob + 1; i <= L2S_WGRAD_MAX_GROUP; ++i) pre.tile0[i] = (int)t;
+  wg_prefix pre;
+  if (fill_tile_prefix(pre, table_host, nprob, [&](const wgp& q) { return variant_tiles(variant, q.Cin, q.Cout, q.KH, q.KW) * (q.split > 1 ? q.split : 1); }) >= (1L << 30)) return L2S_EINVAL;
   // (ring depth 2: with several workgroups per CU the other workgroups cover a load's latency; fewer registers = more of them)
   // KSTEP = MFMA k steps (32 pixels in bf16) per barrier: 2 (64-pixel slices) measured 137.4-139.7 vs 134.9-136.5 img/s for 1 (round 2)
 #define GO(T, KS)                                                                                \
@@ -528,7 +472,7 @@ static int plan_split(const l2s_wgrad_desc& d, int variant, int dtype, size_t ws
 
 extern "C" size_t l2s_wgrad_ws_bytes(const l2s_wgrad_desc* d, int dtype) {
   if (!d) return 0;
-  const int v = variant_of(d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad, d->OH == d->IH && d->OW == d->IW, (long)d->n_img * d->OH * d->OW, d->tile);
+  const int v = variant_of(*d);
   const int split = plan_split(*d, v, dtype, (size_t)1 << 40);
   return split > 1 ? (size_t)split * d->Cout * d->KH * d->KW * d->Cin * 4 : 0;
 }
@@ -536,7 +480,7 @@ extern "C" size_t l2s_wgrad_ws_bytes(const l2s_wgrad_desc* d, int dtype) {
 extern "C" int l2s_conv_wgrad(const l2s_wgrad_desc* d, int dtype, hipStream_t stream) {
   if (!d || !d->dy || !d->x || !d->dw) return L2S_EINVAL;
   if (!prob_ok(prob_of(*d), dtype)) return L2S_EINVAL;
-  const int v = variant_of(d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad, d->OH == d->IH && d->OW == d->IW, (long)d->n_img * d->OH * d->OW, d->tile);
+  const int v = variant_of(*d);
   const int split = plan_split(*d, v, dtype, d->ws ? d->ws_bytes : 0);
 #define GO(T)                                                                                    \
   switch (v) {                                                                                   \

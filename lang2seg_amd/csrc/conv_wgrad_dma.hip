@@ -24,15 +24,11 @@
 //   style: the (tile, slice) units are cut into G equal contiguous ranges, one per workgroup.  A workgroup finishes whole tiles into dW
 //   directly; the at most two tiles it shares with its neighbours go to its two slab slots in the workspace, and a second launch adds
 //   a shared tile's slabs in workgroup order (fixed order: bit-reproducible, no atomics).
-#include "common.h"
-#include "../../include/lang2seg_hip.h"
-#include "wgrad_internal.h"
+#include "wgrad_common.h"
 
 namespace {
+using namespace l2s_wgrad;
 
-typedef l2s_wgrad_prob wgp;
-typedef int i32x4s __attribute__((ext_vector_type(4)));
-constexpr unsigned OOR = 0x80000000u;
 constexpr int BM = 128, BN = 128, BKP = 64, ROWB = 256;
 constexpr int A_BYTES = BKP * ROWB;                 // 64 dY rows
 constexpr int B_ROWS = 68;                          // 66 X rows used (17 requests of 4 rows)
@@ -40,16 +36,9 @@ constexpr int STG = A_BYTES + B_ROWS * ROWB;        // 33 792 B per stage
 constexpr int NPW = 4;                              // DMA requests per wave and slice: 2 x 4 dY rows, 2 x 4 X rows (wave 0: + the X rows 64..67)
 constexpr int TILE_FLOATS = 3 * BM * BN;
 
-// one request = 1 KiB = FOUR 256-byte pixel rows (16 lanes x 16 B each): the vector memory pipe of a CU takes ~16 cycles per wave
-// instruction whatever its width - with one row per `buffer_load_dword ... lds` the 136 requests of a slice cost 0.87 us, more than
-// its MFMAs (knock-outs: requests alone 128 us of the launch, MFMAs alone 101 us, and the two did not overlap)
-__device__ __forceinline__ void dma_rows4(const i32x4s& rsrc, unsigned voff, unsigned lds_) {
-  const unsigned lds = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_);   // (uniform; makes the "s" operand a scalar register even where hipcc kept the value in a VGPR)
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rsrc), "s"(lds) : "memory");
-}
 __device__ __forceinline__ long wg_lo(long g, long U, long G) { return g * U / G; }
 
-template <int KO, int NST>   // NST LDS stages (NST - 1 slices requested ahead); KO bit 3 (8): waves 0 / 4 of workgroup 0 stamp the shader clock (tools/wgrad_stamps.py); knock-outs (tools only): 1 = no MFMAs, 2 = no requests after the prologue, 4 = no fragment reads
+template <int KO, int NST>   // NST LDS stages (NST - 1 slices requested ahead); KO bit 3 (8): waves 0 / 4 of workgroup 0 stamp the shader clock (tools/wgrad_stamps.py); knock-outs (tools only): 1 = no MFMAs, 2 = no requests after the prologue, 4 = no fragment reads, 16 = no offset preparation after the prologue
 __global__ __launch_bounds__(512) void wgrad_row3_dma_kernel(const wgp* __restrict__ tab, const l2s::wgrad_sk_plan plan, float* __restrict__ ws) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -145,10 +134,9 @@ __global__ __launch_bounds__(512) void wgrad_row3_dma_kernel(const wgp* __restri
       sbase += nsl;
       if (sa_ >= sb_) continue;
       const int n = sb_ - sa_;                          // slices of this segment in this pass
-      const int ja = BKP / ohwv, jb = (BKP - ja * ohwv) / Wv, jc = BKP - ja * ohwv - jb * Wv;   // 64 = ja OH Wv + jb Wv + jc
-      i32x4s rdy, rxx;
-      rdy.x = (int)(uintptr_t)p.dy[seg]; rdy.y = (int)((uintptr_t)p.dy[seg] >> 32); rdy.z = 0x7FFFFFFF; rdy.w = 0x00020000;
-      rxx.x = (int)(uintptr_t)p.x[seg]; rxx.y = (int)((uintptr_t)p.x[seg] >> 32); rxx.z = 0x7FFFFFFF; rxx.w = 0x00020000;
+      int ja, jb, jc;
+      slice_step(BKP, ohwv, Wv, ja, jb, jc);            // 64 = ja OH Wv + jb Wv + jc
+      const i32x4s rdy = rsrc(p.dy[seg]), rxx = rsrc(p.x[seg]);
       // this lane's row: virtual pixel -> (image row R = image * OH + row, row, column); the X slab starts one pixel early.  Everything the
       // offset needs is kept incrementally (adds, compares, selects: no multiply in the loop): offR = byte offset of image row R (shifted by
       // the filter row for X), offx = byte offset of column x
@@ -156,10 +144,8 @@ __global__ __launch_bounds__(512) void wgrad_row3_dma_kernel(const wgp* __restri
       const int Rmax = n_img * OH;
       int pR, py, px, offR, offx;
       {
-        const int pix = sa_ * BKP + myrow - (roleA ? 0 : 1);
         int pn;
-        if (pix < 0) { pn = 0; py = 0; px = -1; }
-        else { pn = pix / ohwv; const int rem = pix - pn * ohwv; py = rem / Wv; px = rem - py * Wv; }
+        pixel_place(sa_ * BKP + myrow - (roleA ? 0 : 1), ohwv, Wv, pn, py, px);
         pR = pn * OH + py;
         offR = (pR + (roleA ? 0 : ky - 1)) * rowbytes + (roleA ? co0 : ci0) * 2;
         offx = px * ld2;
@@ -194,11 +180,11 @@ __global__ __launch_bounds__(512) void wgrad_row3_dma_kernel(const wgp* __restri
       auto prep = [&]() { prep_a(); prep_b(); prep_c(); };
       auto request = [&](int stage) {                   // the prepared slice -> LDS stage `stage`
         const unsigned sb = lds0 + (unsigned)(stage * STG);
-        dma_rows4(rdy, vo[0], sb + (unsigned)((8 * wave) * ROWB));
-        dma_rows4(rdy, vo[1], sb + (unsigned)((8 * wave + 4) * ROWB));
-        dma_rows4(rxx, vo[2], sb + (unsigned)(A_BYTES + (4 * wave) * ROWB));
-        dma_rows4(rxx, vo[3], sb + (unsigned)(A_BYTES + (32 + 4 * wave) * ROWB));
-        if (wave == 0) dma_rows4(rxx, vo[4], sb + (unsigned)(A_BYTES + 64 * ROWB));
+        dma_1kib(rdy, vo[0], sb + (unsigned)((8 * wave) * ROWB));
+        dma_1kib(rdy, vo[1], sb + (unsigned)((8 * wave + 4) * ROWB));
+        dma_1kib(rxx, vo[2], sb + (unsigned)(A_BYTES + (4 * wave) * ROWB));
+        dma_1kib(rxx, vo[3], sb + (unsigned)(A_BYTES + (32 + 4 * wave) * ROWB));
+        if (wave == 0) dma_1kib(rxx, vo[4], sb + (unsigned)(A_BYTES + 64 * ROWB));
       };
       // Fragments of a whole slice (2 k steps x (4 dY + 3 x 2 X) fragments = 80 registers): read in the LOAD slot, multiplied in the MUL slot
       uint4 fa[2][4], fb[2][3][2];
@@ -207,24 +193,13 @@ __global__ __launch_bounds__(512) void wgrad_row3_dma_kernel(const wgp* __restri
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const char* q = base + aoff[i] + h * 32 * ROWB;
-            s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(q));
-            s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(q + 16 * ROWB));
-            fa[h][i] = __builtin_bit_cast(uint4, (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
-          }
+          for (int i = 0; i < 4; ++i) fa[h][i] = lds_frag(base + aoff[i] + h * 32 * ROWB, ROWB);
 #pragma unroll
           for (int t = 0; t < 3; ++t)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              const char* q = base + boff[t][j] + h * 32 * ROWB;
-              s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(q));
-              s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(q + 16 * ROWB));
-              fb[h][t][j] = __builtin_bit_cast(uint4, (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
-            }
+            for (int j = 0; j < 2; ++j) fb[h][t][j] = lds_frag(base + boff[t][j] + h * 32 * ROWB, ROWB);
         }
       };
-      // the slice's 48 MFMAs, bare (anything else in this stream costs matrix-pipe time: a wave issues one instruction per four cycles)
       // the slice's 48 MFMAs, bare (anything else in this stream costs matrix-pipe time: a wave issues one instruction per four cycles)
       auto mma_all = [&]() {
 #pragma unroll
@@ -247,19 +222,10 @@ __global__ __launch_bounds__(512) void wgrad_row3_dma_kernel(const wgp* __restri
       // retires ITS share of slice t+1 before the barrier that ends slot 2t+1 (counted vmcnt: only its requests of slice t+2 are younger);
       // a stage is refilled only after every wave has passed a barrier behind the lgkmcnt(0) that retired its reads of that stage.
       const int grp = wave >> 2;
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // (the previous pass's fragments are in registers everywhere)
+      lds_wait(); wg_barrier();                         // (the previous pass's fragments are in registers everywhere)
       auto wait_keep = [&](int younger) {               // everything but this wave's requests of the `younger` youngest slices has landed
-        if (wave == 0) {
-          if (younger >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * (NPW + 1)) : "memory");
-          else if (younger == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (NPW + 1)) : "memory");
-          else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPW + 1) : "memory");
-          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-          if (younger >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * NPW) : "memory");
-          else if (younger == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NPW) : "memory");
-          else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPW) : "memory");
-          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        if (wave == 0) wait_vm_keep<NPW + 1, NST - 2>(younger);
+        else wait_vm_keep<NPW, NST - 2>(younger);
       };
       // prologue: slices 0 .. NST-2 requested, slice NST-1 prepared, this wave's share of slice 0 landed
 #pragma unroll
@@ -267,8 +233,8 @@ __global__ __launch_bounds__(512) void wgrad_row3_dma_kernel(const wgp* __restri
         if (q < n) { prep(); request(q); }
       wait_keep(n - 1 < NST - 2 ? n - 1 : NST - 2);
       if (NST - 1 < n) prep();
-      asm volatile("s_barrier" ::: "memory");
-      if (grp == 1) asm volatile("s_barrier" ::: "memory");              // one slot behind group 0
+      wg_barrier();
+      if (grp == 1) wg_barrier();                       // one slot behind group 0
       int st = 0;
       unsigned long long* stamps = (unsigned long long*)(ws + (long)gridDim.x * 3 * TILE_FLOATS) + grp * 32 * 8;
       const bool stamping = (KO & 8) && blockIdx.x == 0 && (wave & 3) == 0 && lane == 0 && pass == 0 && seg == 0;
@@ -290,11 +256,11 @@ __global__ __launch_bounds__(512) void wgrad_row3_dma_kernel(const wgp* __restri
         stamp(t, 1);
         if (t + NST - 1 < n && !(KO & 2)) request(stq);   // (behind the reads; between the MFMAs of the MUL slot they cost as much matrix-pipe time as they save here)
         stamp(t, 2);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lds_wait();
         if (more) prep_c();
         stamp(t, 3);
         if (grp == 1) wait_keep(younger);
-        asm volatile("s_barrier" ::: "memory");
+        wg_barrier();
         stamp(t, 4);
         __builtin_amdgcn_sched_barrier(0);
         mma_all();
@@ -302,11 +268,11 @@ __global__ __launch_bounds__(512) void wgrad_row3_dma_kernel(const wgp* __restri
         stamp(t, 5);
         if (grp == 0) wait_keep(younger);
         stamp(t, 6);
-        asm volatile("s_barrier" ::: "memory");
+        wg_barrier();
         stamp(t, 7);
         st = st == NST - 1 ? 0 : st + 1;
       }
-      if (grp == 0) asm volatile("s_barrier" ::: "memory");              // group 1's last MUL slot
+      if (grp == 0) wg_barrier();                       // group 1's last MUL slot
     }
 
     // ---- the tile: whole -> dW (+=), shared with a neighbour -> this workgroup's slab ----
@@ -321,14 +287,8 @@ __global__ __launch_bounds__(512) void wgrad_row3_dma_kernel(const wgp* __restri
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const int cil = wn * 32 + j * 16 + fg * 4;
-          float4 v = make_float4(acc[t][i][j][0], acc[t][i][j][1], acc[t][i][j][2], acc[t][i][j][3]);
-          if (full) {
-            float4* q = (float4*)(p.dw + (long)(co0 + col) * Kw + (long)(ky * 3 + t) * p.Cin + ci0 + cil);
-            if (!(p.flags & 1)) { const float4 o = *q; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
-            *q = v;
-          } else {
-            *(float4*)(slab + ((long)(t * BM + col) * BN + cil)) = v;
-          }
+          if (full) dw_store((float4*)(p.dw + (long)(co0 + col) * Kw + (long)(ky * 3 + t) * p.Cin + ci0 + cil), f4(acc[t][i][j]), !(p.flags & 1));
+          else *(float4*)(slab + ((long)(t * BM + col) * BN + cil)) = f4(acc[t][i][j]);
         }
       }
     part = 1;
@@ -370,13 +330,10 @@ __global__ __launch_bounds__(256) void wgrad_row3_reduce_kernel(const wgp* __res
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     for (long g = g0; g <= g1; ++g) {
       const long sl = plan.mode == 1 ? slab0 + g : g * 2 + (wg_lo(g, plan.U, G) >= a ? 0 : 1);
-      const float4 v = ((const float4*)(ws + sl * TILE_FLOATS))[e];
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+      s = add4(s, ((const float4*)(ws + sl * TILE_FLOATS))[e]);
     }
     const int f = e * 4, t = f / (BM * BN), col = (f - t * BM * BN) / BN, cil = f % BN;
-    float4* q = (float4*)(p.dw + (long)(cot * BM + col) * Kw + (long)(ky * 3 + t) * p.Cin + cit * BN + cil);
-    if (!(p.flags & 1)) { const float4 o = *q; s.x += o.x; s.y += o.y; s.z += o.z; s.w += o.w; }
-    *q = s;
+    dw_store((float4*)(p.dw + (long)(cot * BM + col) * Kw + (long)(ky * 3 + t) * p.Cin + cit * BN + cil), s, !(p.flags & 1));
   }
 }
 
@@ -436,13 +393,7 @@ int wgrad_row3_dma_launch(const l2s_wgrad_prob* tab_dev, const l2s_wgrad_prob* t
   long nslabs = plan.mode == 1 ? (long)G * (plan.Q + (plan.r ? 1 : 0)) : (long)G * 2;
   if (plan.mode == 1 && ws_bytes < (size_t)nslabs * TILE_FLOATS * sizeof(float)) { plan.mode = 0; nslabs = (long)G * 2; }   // (many groups: the contiguous plan needs 2 slabs per workgroup)
   if (!ws || ws_bytes < (size_t)nslabs * TILE_FLOATS * sizeof(float)) return L2S_EINVAL;
-#define GO(KO_, NST_)                                                                                                                          \
-  {                                                                                                                                            \
-    constexpr size_t lds = (size_t)NST_ * STG;                                                                                                 \
-    static bool attr_done = false;                                                                                                             \
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)wgrad_row3_dma_kernel<KO_, NST_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; } \
-    L2S_LAUNCH((wgrad_row3_dma_kernel<KO_, NST_>), dim3(G), dim3(512), lds, st, tab_dev, plan, ws);                                            \
-  }
+#define GO(KO_, NST_) WGRAD_LAUNCH((wgrad_row3_dma_kernel<KO_, NST_>), dim3(G), dim3(512), (size_t)NST_ * STG, st, tab_dev, plan, ws);
 #ifdef L2S_TOOLS
   switch (l2s_knobs::row3_form) {   // knock-out builds of the kernel for tools/wgrad_stamps.py (their results are garbage); not in the product library
     case 1: GO(1, 4) break; case 2: GO(2, 4) break; case 5: GO(5, 4) break; case 6: GO(6, 4) break; case 7: GO(7, 4) break;

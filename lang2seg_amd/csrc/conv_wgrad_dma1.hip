@@ -19,25 +19,15 @@
 //   slice's 24 fragment reads + the four requests of the slice two ahead, MUL = 32 bare MFMAs; counted vmcnt.
 // * Every accumulator sums its pixels in order, segment 0 first: bit-reproducible; equal to the register-staged tile's sums wherever that one
 //   was not split.
-#include "common.h"
-#include "../../include/lang2seg_hip.h"
-#include "wgrad_internal.h"
+#include "wgrad_common.h"
 
 namespace {
+using namespace l2s_wgrad;
 
-typedef l2s_wgrad_prob wgp;
-typedef int i32x4s __attribute__((ext_vector_type(4)));
-constexpr unsigned OOR = 0x80000000u;
 constexpr int BM = 256, BN = 256, KP = 32, ROWB = 512;
 constexpr int A_BYTES = KP * ROWB;                  // 16 KiB: 32 dY rows
 constexpr int STG = 2 * A_BYTES;                    // + 32 X rows
 constexpr int NP = 4;                               // requests per wave and slice
-
-__device__ __forceinline__ void dma_rows2(const i32x4s& rsrc, unsigned voff, unsigned lds_) {
-  const unsigned lds = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rsrc), "s"(lds) : "memory");
-}
-__device__ __forceinline__ void wgb() { asm volatile("s_barrier" ::: "memory"); }
 
 template <int NST>   // LDS stages: NST - 1 slices are requested ahead
 __global__ __launch_bounds__(512) void wgrad_1x1_dma_kernel(const wgp* __restrict__ tab, const l2s::wgrad_tile_prefix pre) {
@@ -47,27 +37,15 @@ __global__ __launch_bounds__(512) void wgrad_1x1_dma_kernel(const wgp* __restric
   const int grp = wave >> 2;
   const int wm = wave >> 1, wn = wave & 1;            // 4 x 2 waves, wave tile 64 (co) x 128 (ci)
   const int fr = lane & 15, fg = lane >> 4;
-  // XCD-aware order: workgroup b runs on XCD b % 8; XCD x takes the x-th contiguous eighth of the tile list, whose neighbours share a dY or an X
-  // slab (operands far larger than one XCD's 4 MiB L2 are otherwise served at the fabric's ~33 GB/s per CU)
-  int bid;
-  {
-    const int G = pre.tile0[pre.n], b = (int)blockIdx.x, x = b & 7, slot = b >> 3, q = G >> 3, r = G & 7;
-    bid = x * q + min(x, r) + slot;
-  }
-  int lo = 0, hi = pre.n;                             // tile0[lo] <= bid < tile0[hi]
-  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (pre.tile0[mid] <= bid) lo = mid; else hi = mid; }
-  const wgp p = tab[lo];
-  const int t = bid - pre.tile0[lo];
+  int t;                                              // XCD-aware order (tile_of): the neighbours in the tile list share a dY or an X slab
+  const wgp p = tab[tile_of(pre, (int)blockIdx.x, t)];
   const int co_tiles = p.Cout / BM;
   const int co0 = (t % co_tiles) * BM, ci0 = (t / co_tiles) * BN;
   const int M0 = p.n_img[0] * p.OH[0] * p.OW[0], M1 = p.nseg > 1 ? p.n_img[1] * p.OH[1] * p.OW[1] : 0;
   const int ns0 = (M0 + KP - 1) / KP, KT = ns0 + (M1 + KP - 1) / KP;
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  auto desc = [](const void* base, long bytes) {
-    i32x4s r; r.x = (int)(uintptr_t)base; r.y = (int)((uintptr_t)base >> 32); r.z = (int)bytes; r.w = 0x00020000; return r;
-  };
-  const i32x4s rdy0 = desc(p.dy[0], (long)M0 * p.lddy[0] * 2L), rx0 = desc(p.x[0], (long)M0 * p.ldx[0] * 2L);
-  const i32x4s rdy1 = desc(p.nseg > 1 ? p.dy[1] : p.dy[0], (long)M1 * p.lddy[p.nseg > 1] * 2L), rx1 = desc(p.nseg > 1 ? p.x[1] : p.x[0], (long)M1 * p.ldx[p.nseg > 1] * 2L);
+  const i32x4s rdy0 = rsrc(p.dy[0], (long)M0 * p.lddy[0] * 2L), rx0 = rsrc(p.x[0], (long)M0 * p.ldx[0] * 2L);
+  const i32x4s rdy1 = rsrc(p.nseg > 1 ? p.dy[1] : p.dy[0], (long)M1 * p.lddy[p.nseg > 1] * 2L), rx1 = rsrc(p.nseg > 1 ? p.x[1] : p.x[0], (long)M1 * p.ldx[p.nseg > 1] * 2L);
   // ---- DMA lane constants: lane l of a request writes 16 bytes at LDS offset 16 l of the request's two rows: row g = l >> 5, physical chunk
   // l & 31; it fetches source chunk physical ^ 2 (r & 15), r = the row's index in its slab.  Wave w requests rows 2 w + g and 16 + 2 w + g of
   // both slabs: r & 15 = 2 w + g for all four requests.
@@ -94,13 +72,13 @@ __global__ __launch_bounds__(512) void wgrad_1x1_dma_kernel(const wgp* __restric
     for (int q = 0; q < 2; ++q) {
       const int r = rowq[q];
       const unsigned va = r < nv ? (unsigned)(((m0 + r) * ldd + co0 + sc * 8) * 2) : OOR;   // (< 2^31: prob_ok)
-      dma_rows2(rd, va, sb + (unsigned)((wave + 8 * q) * 1024));
+      dma_1kib(rd, va, sb + (unsigned)((wave + 8 * q) * 1024));
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int r = rowq[q];
       const unsigned vb = r < nv ? (unsigned)(((m0 + r) * ldxx + ci0 + sc * 8) * 2) : OOR;
-      dma_rows2(rxx, vb, sb + (unsigned)(A_BYTES + (wave + 8 * q) * 1024));
+      dma_1kib(rxx, vb, sb + (unsigned)(A_BYTES + (wave + 8 * q) * 1024));
     }
   };
   f32x4 acc[4][8];
@@ -109,17 +87,12 @@ __global__ __launch_bounds__(512) void wgrad_1x1_dma_kernel(const wgp* __restric
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   uint4 fa[4], fb[8];
-  auto frag = [&](const char* q) {
-    const s16x4 l4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(q));
-    const s16x4 h4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(q + 16 * ROWB));
-    return __builtin_bit_cast(uint4, (s16x8){l4[0], l4[1], l4[2], l4[3], h4[0], h4[1], h4[2], h4[3]});
-  };
   auto read_all = [&](int stage) {
     const char* base = smem + stage * STG;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) fa[i] = frag(base + aoff[i]);
+    for (int i = 0; i < 4; ++i) fa[i] = lds_frag(base + aoff[i], ROWB);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) fb[j] = frag(base + boff[j]);
+    for (int j = 0; j < 8; ++j) fb[j] = lds_frag(base + boff[j], ROWB);
   };
   auto mma_all = [&]() {
 #pragma unroll
@@ -129,35 +102,30 @@ __global__ __launch_bounds__(512) void wgrad_1x1_dma_kernel(const wgp* __restric
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fb[j]), __builtin_bit_cast(bf16x8, fa[i]), acc[i][j], 0, 0, 0);
   };
   // ---- pipeline: slices 0 .. NST-2 requested; everybody waits for its share of slice 0 ----
-  // wait until at most `younger` slices' requests of this wave are outstanding (they complete in order)
-  auto wait_keep = [&](int younger) {
-    if (younger >= 2 && NST >= 4) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");
-    else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
+  auto wait_keep = [&](int younger) { wait_vm_keep<NP, NST - 2>(younger); };   // (at most NST - 2 slices' requests stay outstanding)
 #pragma unroll
   for (int s = 0; s < NST - 1; ++s)
     if (s < KT) request(s, s);
   wait_keep(min(NST - 2, KT - 1));                      // slice 0 landed
-  wgb();
-  if (grp == 1) wgb();                                  // one slot behind group 0
+  wg_barrier();
+  if (grp == 1) wg_barrier();                           // one slot behind group 0
   int st = 0;
   for (int ts = 0; ts < KT; ++ts) {
     const int stn = st == 0 ? NST - 1 : st - 1;         // (ts + NST - 1) % NST: the stage of slice ts - 1
     read_all(st);
     if (ts + NST - 1 < KT) request(stn, ts + NST - 1);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lds_wait();
     const int younger = max(0, min(NST - 2, KT - 2 - ts));   // requests that may stay in flight behind slice ts + 1
     if (grp == 1) wait_keep(younger);                   // slice ts + 1 landed
-    wgb();
+    wg_barrier();
     __builtin_amdgcn_sched_barrier(0);
     mma_all();
     __builtin_amdgcn_sched_barrier(0);
     if (grp == 0) wait_keep(younger);
-    wgb();
+    wg_barrier();
     st = st == NST - 1 ? 0 : st + 1;
   }
-  if (grp == 0) wgb();                                  // group 1's last MUL slot
+  if (grp == 0) wg_barrier();                           // group 1's last MUL slot
   // ---- the tile: lane = output channel co (fr), four consecutive input channels (fg) per accumulator ----
   const bool overwrite = p.flags & 1;
 #pragma unroll
@@ -166,10 +134,7 @@ __global__ __launch_bounds__(512) void wgrad_1x1_dma_kernel(const wgp* __restric
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int ci = ci0 + wn * 128 + j * 16 + fg * 4;
-      float4* q = (float4*)(p.dw + co * p.Cin + ci);
-      float4 v = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-      if (!overwrite) { const float4 o = *q; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
-      *q = v;
+      dw_store((float4*)(p.dw + co * p.Cin + ci), f4(acc[i][j]), !overwrite);
     }
   }
 }
@@ -189,19 +154,11 @@ bool wgrad_1x1_dma_ok(const l2s_wgrad_prob& q) {
 long wgrad_1x1_dma_tiles(int Cin, int Cout) { return (long)(Cout / BM) * (Cin / BN); }
 
 int wgrad_1x1_dma_launch(const l2s_wgrad_prob* tab_dev, const l2s_wgrad_prob* tab_host, int nprob, hipStream_t st) {
+  for (int i = 0; i < nprob; ++i) if (!wgrad_1x1_dma_ok(tab_host[i])) return L2S_EINVAL;
   wgrad_tile_prefix pre;
-  pre.n = nprob;
-  long t = 0;
-  for (int i = 0; i < nprob; ++i) {
-    if (!wgrad_1x1_dma_ok(tab_host[i])) return L2S_EINVAL;
-    pre.tile0[i] = (int)t;
-    t += wgrad_1x1_dma_tiles(tab_host[i].Cin, tab_host[i].Cout);
-  }
-  for (int i = nprob; i <= L2S_WGRAD_MAX_GROUP; ++i) pre.tile0[i] = (int)t;
-  static bool attr = false;
+  const long t = fill_tile_prefix(pre, tab_host, nprob, [](const wgp& q) { return wgrad_1x1_dma_tiles(q.Cin, q.Cout); });
   const size_t lds = (size_t)4 * STG;                  // four stages: 128 KiB, three slices (96 KB) in flight per CU
-  if (!attr) { (void)hipFuncSetAttribute((const void*)wgrad_1x1_dma_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-  L2S_LAUNCH(wgrad_1x1_dma_kernel<4>, dim3((unsigned)t), dim3(512), lds, st, tab_dev, pre);
+  WGRAD_LAUNCH(wgrad_1x1_dma_kernel<4>, dim3((unsigned)t), dim3(512), lds, st, tab_dev, pre);
   return l2s_check_launch();
 }
 
