@@ -674,6 +674,19 @@ typedef struct {
  * or any beam at t == T - 1, is appended to `done` and its sum becomes -1000.  1 <= B <= min(16, V1), T <= 64, 0 <= t < T.
  * A NaN logit is no candidate and a NaN sum ranks last (as -inf): the outputs stay well defined and in range. */
 int l2s_decode_beam_step(const l2s_beam_step_args* a, hipStream_t s);
+/* Device, one workgroup per detection: l2s_decode_beam_step for every live detection of a sentence (detection d is live iff
+ * row0 + d < *count, see the rows section below; a dead one is neither read nor written, the grid is `rows`).  `a` describes detection 0;
+ * detection d uses logits rows [d B, d B + B) of [rows * B][ld_logits], beam_seq / beam_seq_logprobs [rows][T][B], beam_logprobs_sum
+ * [rows][B], next_tokens [rows * B], parents [rows][B], done [rows][B * T] records, done_count [rows] and rows [d B, d B + B) of every
+ * state array (gathered by parent inside the group).  The same device function: a detection gets the bits l2s_decode_beam_step gives it. */
+int l2s_decode_beam_step_rows(const l2s_beam_step_args* a, int rows, int row0, const int* count, hipStream_t s);
+/* Device, one workgroup per detection: the final ordering of CaptionModel.py:123.  The done_count[d] (clamped to B * T) records of
+ * detection d ordered by p descending, equal p in completion order; the first beam_n[d] = min(B, done_count[d]) go to beam_seq int64
+ * [rows][B][T], beam_logps f32 [rows][B][T] and beam_p f32 [rows][B] (zeros behind beam_n[d]), and the best one to seq int64 [rows][T]
+ * (zero from its first 0 on) and logprobs f32 [rows][T] (kept up to and with that 0, zero behind it): l2s_decode_pick_rows' layout.
+ * B <= 16, T <= 64.  Dead detections are not written. */
+int l2s_decode_beam_finish_rows(const int* done, const int* done_count, int B, int T, int rows, int row0, const int* count,
+                                int64_t* beam_seq, float* beam_logps, float* beam_p, int* beam_n, int64_t* seq, float* logprobs, hipStream_t s);
 /* Device.  dst [H][W] = src [ih][iw] (uint8) resized by PIL NEAREST (csrc/pil_resize.h pil_nearest_src, the rule of the loader's masks). */
 int l2s_mask_resize_nearest(const uint8_t* src, int ih, int iw, uint8_t* dst, int H, int W, hipStream_t s);
 
@@ -720,6 +733,18 @@ int l2s_lstm_cell_rows(const l2s_lstm_rows* a, int R, int rows, int row0, const 
  * kernel's summation order: the same bits as the single-row launch.  L <= 256, ld_res >= R. */
 int l2s_cap_att_apply_rows(const float* att, const float* dots, float* att_res, int ld_res, int rows, int row0, const int* count, int L, int R,
                            hipStream_t s);
+/* The step on GROUPS (beam search on rows): `rows` state rows, `group` consecutive ones per detection (rows % group == 0).  Row r reads
+ * its own att_h / dots / sums / states and detection r / group's patt, P, att and (the cell) pre2, and is live iff
+ * row0 + r / group < *count.  The bodies of the *_rows entries, which are the group == 1 case: the same bits as those entries on operands
+ * replicated `group` times.  patt, P and att have rows / group rows of [L][.]; the cell's pre2 has rows / group rows of ld_pre2 floats
+ * (ld_pre2 = 0: one row for all), read at row r / group, while pre, the segments' x, c_prev, c and h keep one row per state row. */
+int l2s_cap_att_dots_groups(const float* patt, const float* att_h, int ld_att_h, const float* aw, const float* ab, int rows, int group,
+                            int row0, const int* count, int L, int D, float* dots, hipStream_t s);
+int l2s_cap_apply_gates_groups(const float* P, const float* dots, const float* b_a2c, const float* sums, int ld_sums, const float* c_prev,
+                               float* c, float* h, int rows, int group, int row0, const int* count, int L, int R, hipStream_t s);
+int l2s_cap_att_apply_groups(const float* att, const float* dots, float* att_res, int ld_res, int rows, int group, int row0,
+                             const int* count, int L, int R, hipStream_t s);
+int l2s_lstm_cell_groups(const l2s_lstm_rows* a, int R, int rows, int group, int row0, const int* count, hipStream_t s);
 
 /* ---------------------------------------------------------------- launch tape / streams ----- */
 /* `to` waits (device side) for everything enqueued so far on `from`; fork or join of the step's branches */

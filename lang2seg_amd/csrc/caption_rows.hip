@@ -102,12 +102,12 @@ __device__ __forceinline__ void cell_rows_seg(const float* const (&xr)[MT], cons
   }
 }
 template <int MT, bool VEC>
-__global__ __launch_bounds__(256) void lstm_cell_rows_kernel(CellR a, int R, int rows, int row0, const int* __restrict__ count) {
+__global__ __launch_bounds__(256) void lstm_cell_rows_kernel(CellR a, int R, int rows, int group, int row0, const int* __restrict__ count) {
   __shared__ float red[4][MT][4][64];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, j = lane & 15, kq = lane >> 4;
   const int u0 = blockIdx.x * CELL_U, m0 = blockIdx.y * (16 * MT);
-  const int nlive = live_rows(rows, row0, count);
-  if (m0 >= nlive) return;                               // (the whole workgroup: before any barrier)
+  const int nlive = live_rows(rows / group, row0, count) * group;      // group rows per detection (l2s_lstm_cell_groups; 1: a row is a detection)
+  if (m0 >= nlive) return;                              // (the whole workgroup: before any barrier)
   const long wrow = (long)(j >> 2) * R + min(u0 + (j & 3), R - 1);
   floatx4 acc[MT];
 #pragma unroll
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void lstm_cell_rows_kernel(CellR a, int R, int
         const int at = (ml >> 2) * 16 + 4 * q + u;
         float v = ((red[0][t][ml & 3][at] + red[1][t][ml & 3][at]) + red[2][t][ml & 3][at]) + red[3][t][ml & 3][at];
         if (a.pre) v += a.pre[(long)m * a.ld_pre + q * R + unit];
-        if (a.pre2) v += a.pre2[(long)m * a.ld_pre2 + q * R + unit];
+        if (a.pre2) v += a.pre2[(long)(m / group) * a.ld_pre2 + q * R + unit];
         if (a.add0) v += a.add0[q * R + unit];
         if (a.add1) v += a.add1[q * R + unit];
         g[q] = v;
@@ -169,8 +169,8 @@ static bool rows_seg_ok(const l2s_rows_seg& g, int rows) {
 static bool rows_seg_vec(const l2s_rows_seg& g) {
   return g.n == 0 || !((g.n & 3) || (g.ld & 3) || (g.ldx & 3) || ((uintptr_t)g.x & 15) || ((uintptr_t)g.w & 15));
 }
-extern "C" int l2s_lstm_cell_rows(const l2s_lstm_rows* a, int R, int rows, int row0, const int* count, hipStream_t s) {
-  if (!a || R < 1 || rows < 1 || row0 < 0 || !a->c_prev || !a->c || !a->h || !rows_seg_ok(a->seg[0], rows) || !rows_seg_ok(a->seg[1], rows) ||
+static int lstm_cell_launch(const l2s_lstm_rows* a, int R, int rows, int group, int row0, const int* count, hipStream_t s) {
+  if (!a || R < 1 || rows < 1 || group < 1 || rows % group || row0 < 0 || !a->c_prev || !a->c || !a->h || !rows_seg_ok(a->seg[0], rows) || !rows_seg_ok(a->seg[1], rows) ||
       cdiv(rows, 16) > 65535)
     return L2S_EINVAL;
   if (rows > 1 && (a->ld_c_prev < R || a->ld_c < R || a->ld_h < R || (a->pre && a->ld_pre != 0 && a->ld_pre < 4 * R) ||
@@ -183,12 +183,20 @@ extern "C" int l2s_lstm_cell_rows(const l2s_lstm_rows* a, int R, int rows, int r
   const bool vec = rows_seg_vec(a->seg[0]) && rows_seg_vec(a->seg[1]);
   const dim3 g1(cdiv(R, CELL_U), cdiv(rows, 16)), g2(cdiv(R, CELL_U), cdiv(rows, 32));
   if (rows <= 16) {
-    if (vec) L2S_LAUNCH((lstm_cell_rows_kernel<1, true>), g1, dim3(256), 0, s, k, R, rows, row0, count);
-    else L2S_LAUNCH((lstm_cell_rows_kernel<1, false>), g1, dim3(256), 0, s, k, R, rows, row0, count);
+    if (vec) L2S_LAUNCH((lstm_cell_rows_kernel<1, true>), g1, dim3(256), 0, s, k, R, rows, group, row0, count);
+    else L2S_LAUNCH((lstm_cell_rows_kernel<1, false>), g1, dim3(256), 0, s, k, R, rows, group, row0, count);
   } else {
-    if (vec) L2S_LAUNCH((lstm_cell_rows_kernel<2, true>), g2, dim3(256), 0, s, k, R, rows, row0, count);
-    else L2S_LAUNCH((lstm_cell_rows_kernel<2, false>), g2, dim3(256), 0, s, k, R, rows, row0, count);
+    if (vec) L2S_LAUNCH((lstm_cell_rows_kernel<2, true>), g2, dim3(256), 0, s, k, R, rows, group, row0, count);
+    else L2S_LAUNCH((lstm_cell_rows_kernel<2, false>), g2, dim3(256), 0, s, k, R, rows, group, row0, count);
   }
   return l2s_check_launch();
+}
+extern "C" int l2s_lstm_cell_rows(const l2s_lstm_rows* a, int R, int rows, int row0, const int* count, hipStream_t s) {
+  return lstm_cell_launch(a, R, rows, 1, row0, count, s);
+}
+// the cell on groups of `group` consecutive rows per detection (beam search on rows): row m is live iff detection m / group is, and pre2
+// (the per-detection term: the top-down captioner's fcrow) is read at row m / group; everything else is per row as above
+extern "C" int l2s_lstm_cell_groups(const l2s_lstm_rows* a, int R, int rows, int group, int row0, const int* count, hipStream_t s) {
+  return lstm_cell_launch(a, R, rows, group, row0, count, s);
 }
 

@@ -8,7 +8,8 @@
 // The gate block, the LSTM cell and the softmax pieces are recur.h's; cap_recur.hip runs the att2in2 recurrence as one resident launch.
 // The attention dots, the softmax + weighted sum and the softmax + gates also run on rows, one row per detection (l2s_cap_att_dots_rows,
 // l2s_cap_att_apply_rows, l2s_cap_apply_gates_rows for --describe / --expr_score): the same body instantiated with a row index, so a row
-// has the bits the single-row kernel gives it.
+// has the bits the single-row kernel gives it.  The *_groups entries (beam search on rows, nets/caption_rows.py) are the rows bodies with a
+// divisor: state row r belongs to detection r / group, reads that detection's patt / P / att and is live iff the detection is.
 #include "common.h"
 #include "../../include/lang2seg_hip.h"
 #include "recur.h"
@@ -27,12 +28,13 @@ namespace {
 // a link of the train step's critical path, and the stores that backward reads (tanh_ws, weight, save).
 template <bool ROWS, bool TRAIN>
 __device__ __forceinline__ void cap_att_dots(const float* patt, const float* att_h, int ld_att_h, const float* aw,
-                                             const float* ab, int row0, const int* count, int L, int D, float* tanh_ws,
+                                             const float* ab, int row0, const int* count, int group, int L, int D, float* tanh_ws,
                                              float* dots) {
   if (TRAIN) __builtin_amdgcn_s_setprio(3);   // a link of the caption branch's dependent chain (the step's critical path): issue ahead of co-resident GEMM waves
   const int r = ROWS ? blockIdx.y : 0, l = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (l >= L || (ROWS && !row_live(r, row0, count))) return;
-  patt += (long)r * L * D;
+  const int dr = ROWS ? r / group : 0;
+  if (l >= L || (ROWS && !row_live(dr, row0, count))) return;
+  patt += (long)dr * L * D;
   att_h += (long)r * ld_att_h;
   float s = 0.f;
   for (int d = lane; d < D; d += 64) {
@@ -44,19 +46,20 @@ __device__ __forceinline__ void cap_att_dots(const float* patt, const float* att
   if (lane == 0) dots[(long)r * 256 + l] = s + ab[0];
 }
 template <bool ROWS, bool TRAIN>
-__device__ __forceinline__ void cap_att_apply(const float* att, const float* dots, int row0, const int* count, int L,
+__device__ __forceinline__ void cap_att_apply(const float* att, const float* dots, int row0, const int* count, int group, int L,
                                               int D, float* weight, float* att_res, int ld_res) {
   if (TRAIN) __builtin_amdgcn_s_setprio(3);
   __shared__ float w[256];
   __shared__ float red[4];
   __shared__ float part[4][64];
   const int r = ROWS ? blockIdx.y : 0, tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
-  if (ROWS && !row_live(r, row0, count)) return;
+  const int dr = ROWS ? r / group : 0;
+  if (ROWS && !row_live(dr, row0, count)) return;
   const float wt = block_softmax(dots + (long)r * 256, L, red);
   if (tid < L) { w[tid] = wt; if (TRAIN && blockIdx.x == 0) weight[tid] = wt; }
   __syncthreads();
   const int d = blockIdx.x * 64 + lane;
-  att += (long)r * L * D;
+  att += (long)dr * L * D;
   float s = 0.f;
   if (d < D) for (int l = g; l < L; l += 4) s = fmaf(w[l], att[(long)l * D + d], s);
   part[g][lane] = s;
@@ -65,19 +68,28 @@ __device__ __forceinline__ void cap_att_apply(const float* att, const float* dot
 }
 __global__ __launch_bounds__(256) void cap_att_dots_kernel(const float* __restrict__ patt, const float* __restrict__ att_h, const float* __restrict__ aw,
                                                           const float* __restrict__ ab, int L, int D, float* tanh_ws, float* dots) {
-  cap_att_dots<false, true>(patt, att_h, 0, aw, ab, 0, nullptr, L, D, tanh_ws, dots);
+  cap_att_dots<false, true>(patt, att_h, 0, aw, ab, 0, nullptr, 1, L, D, tanh_ws, dots);
 }
 __global__ __launch_bounds__(256) void cap_att_dots_rows_kernel(const float* __restrict__ patt, const float* __restrict__ att_h, int ld_att_h,
                                                                const float* __restrict__ aw, const float* __restrict__ ab, int row0,
                                                                const int* __restrict__ count, int L, int D, float* dots) {
-  cap_att_dots<true, false>(patt, att_h, ld_att_h, aw, ab, row0, count, L, D, nullptr, dots);
+  cap_att_dots<true, false>(patt, att_h, ld_att_h, aw, ab, row0, count, 1, L, D, nullptr, dots);
+}
+__global__ __launch_bounds__(256) void cap_att_dots_groups_kernel(const float* __restrict__ patt, const float* __restrict__ att_h, int ld_att_h,
+                                                                 const float* __restrict__ aw, const float* __restrict__ ab, int row0,
+                                                                 const int* __restrict__ count, int group, int L, int D, float* dots) {
+  cap_att_dots<true, false>(patt, att_h, ld_att_h, aw, ab, row0, count, group, L, D, nullptr, dots);
 }
 __global__ __launch_bounds__(256) void cap_att_apply_kernel(const float* __restrict__ att, const float* __restrict__ dots, int L, int D, float* weight, float* att_res) {
-  cap_att_apply<false, true>(att, dots, 0, nullptr, L, D, weight, att_res, 0);
+  cap_att_apply<false, true>(att, dots, 0, nullptr, 1, L, D, weight, att_res, 0);
 }
 __global__ __launch_bounds__(256) void cap_att_apply_rows_kernel(const float* __restrict__ att, const float* __restrict__ dots, float* att_res, int ld_res,
                                                                 int row0, const int* __restrict__ count, int L, int D) {
-  cap_att_apply<true, false>(att, dots, row0, count, L, D, nullptr, att_res, ld_res);
+  cap_att_apply<true, false>(att, dots, row0, count, 1, L, D, nullptr, att_res, ld_res);
+}
+__global__ __launch_bounds__(256) void cap_att_apply_groups_kernel(const float* __restrict__ att, const float* __restrict__ dots, float* att_res, int ld_res,
+                                                                  int row0, const int* __restrict__ count, int group, int L, int D) {
+  cap_att_apply<true, false>(att, dots, row0, count, group, L, D, nullptr, att_res, ld_res);
 }
 // backward: (A) dweight[l] = dres . att[l] (one wave per l); (B) D/64 workgroups: softmax backward over L (recomputed), then the
 // per-channel accumulations with 4 l-groups per 64 channels.
@@ -303,13 +315,14 @@ __global__ __launch_bounds__(1024) void cap_att_bwd_step_kernel(const float* __r
 template <bool ROWS, bool TRAIN>
 __device__ __forceinline__ void cap_apply_gates(const float* P, const float* dots, const float* b,
                                                 const float* s, int ld_s, const float* c_prev, float* c, float* h,
-                                                float* save, float* weight, int row0, const int* count, int L, int R) {
+                                                float* save, float* weight, int row0, const int* count, int group, int L, int R) {
   if (TRAIN) __builtin_amdgcn_s_setprio(3);
   __shared__ float w[256];
   __shared__ float red[4];
   __shared__ float p0[16][17], p1[16][17];
   const int r = ROWS ? blockIdx.y : 0, tid = threadIdx.x, dl = tid & 15, lg = tid >> 4;
-  if (ROWS && !row_live(r, row0, count)) return;
+  const int dr = ROWS ? r / group : 0;
+  if (ROWS && !row_live(dr, row0, count)) return;
   const float wt = block_softmax(dots + (long)r * 256, L, red);
   w[tid] = tid < L ? wt : 0.f;
   if (TRAIN && blockIdx.x == 0 && tid < L) weight[tid] = wt;
@@ -317,7 +330,7 @@ __device__ __forceinline__ void cap_apply_gates(const float* P, const float* dot
   const int j = blockIdx.x * 16 + dl;
   float a0 = 0.f, a1 = 0.f;
   if (j < R) {
-    const float* q = P + (long)r * L * 2 * R + j;
+    const float* q = P + (long)dr * L * 2 * R + j;
     for (int l = lg; l < L; l += 16) {
       const float wl = w[l];
       a0 = fmaf(wl, q[(long)l * 2 * R], a0);
@@ -340,12 +353,17 @@ __device__ __forceinline__ void cap_apply_gates(const float* P, const float* dot
 __global__ __launch_bounds__(256) void cap_apply_gates_kernel(const float* __restrict__ P, const float* __restrict__ dots, const float* __restrict__ b,
                                                              const float* __restrict__ s, const float* __restrict__ c_prev, float* c, float* h,
                                                              float* save, float* weight, int L, int R) {
-  cap_apply_gates<false, true>(P, dots, b, s, 0, c_prev, c, h, save, weight, 0, nullptr, L, R);
+  cap_apply_gates<false, true>(P, dots, b, s, 0, c_prev, c, h, save, weight, 0, nullptr, 1, L, R);
 }
 __global__ __launch_bounds__(256) void cap_apply_gates_rows_kernel(const float* __restrict__ P, const float* __restrict__ dots, const float* __restrict__ b,
                                                                   const float* __restrict__ s, int ld_s, const float* __restrict__ c_prev, float* c,
                                                                   float* h, int row0, const int* __restrict__ count, int L, int R) {
-  cap_apply_gates<true, false>(P, dots, b, s, ld_s, c_prev, c, h, nullptr, nullptr, row0, count, L, R);
+  cap_apply_gates<true, false>(P, dots, b, s, ld_s, c_prev, c, h, nullptr, nullptr, row0, count, 1, L, R);
+}
+__global__ __launch_bounds__(256) void cap_apply_gates_groups_kernel(const float* __restrict__ P, const float* __restrict__ dots, const float* __restrict__ b,
+                                                                    const float* __restrict__ s, int ld_s, const float* __restrict__ c_prev, float* c,
+                                                                    float* h, int row0, const int* __restrict__ count, int group, int L, int R) {
+  cap_apply_gates<true, false>(P, dots, b, s, ld_s, c_prev, c, h, nullptr, nullptr, row0, count, group, L, R);
 }
 // backward (1): the gate backward of cap_gates_bwd_kernel recomputed by every workgroup into LDS (2R values; workgroup 0 also stores
 // dsums / da2c / dc_prev), then one wave per location: dweight[l] = P[l] . da2c.   R <= 1024.
@@ -575,6 +593,14 @@ extern "C" int l2s_cap_att_dots_rows(const float* patt, const float* att_h, int 
   L2S_LAUNCH(cap_att_dots_rows_kernel, dim3(cdiv(L, 4), rows), dim3(256), 0, s, patt, att_h, ld_att_h, aw, ab, row0, count, L, D, dots);
   return l2s_check_launch();
 }
+extern "C" int l2s_cap_att_dots_groups(const float* patt, const float* att_h, int ld_att_h, const float* aw, const float* ab, int rows, int group,
+                                       int row0, const int* count, int L, int D, float* dots, hipStream_t s) {
+  if (!patt || !att_h || !aw || !ab || !dots || rows < 1 || rows > 65535 || group < 1 || rows % group || row0 < 0 || L < 1 || L > 256 || D < 1 ||
+      ld_att_h < D)
+    return L2S_EINVAL;
+  L2S_LAUNCH(cap_att_dots_groups_kernel, dim3(cdiv(L, 4), rows), dim3(256), 0, s, patt, att_h, ld_att_h, aw, ab, row0, count, group, L, D, dots);
+  return l2s_check_launch();
+}
 extern "C" int l2s_cap_apply_gates_fwd(const float* P, const float* dots, const float* b_a2c, const float* sums, const float* c_prev, float* c, float* h,
                                        float* save, float* weight, int L, int R, hipStream_t s) {
   if (L > 256) return L2S_EINVAL;
@@ -587,6 +613,15 @@ extern "C" int l2s_cap_apply_gates_rows(const float* P, const float* dots, const
       ld_sums < 5 * R)
     return L2S_EINVAL;
   L2S_LAUNCH(cap_apply_gates_rows_kernel, dim3(cdiv(R, 16), rows), dim3(256), 0, s, P, dots, b_a2c, sums, ld_sums, c_prev, c, h, row0, count, L, R);
+  return l2s_check_launch();
+}
+extern "C" int l2s_cap_apply_gates_groups(const float* P, const float* dots, const float* b_a2c, const float* sums, int ld_sums, const float* c_prev,
+                                          float* c, float* h, int rows, int group, int row0, const int* count, int L, int R, hipStream_t s) {
+  if (!P || !dots || !b_a2c || !sums || !c_prev || !c || !h || rows < 1 || rows > 65535 || group < 1 || rows % group || row0 < 0 || L < 1 ||
+      L > 256 || R < 1 || R > 1024 || ld_sums < 5 * R)
+    return L2S_EINVAL;
+  L2S_LAUNCH(cap_apply_gates_groups_kernel, dim3(cdiv(R, 16), rows), dim3(256), 0, s, P, dots, b_a2c, sums, ld_sums, c_prev, c, h, row0, count, group,
+             L, R);
   return l2s_check_launch();
 }
 extern "C" int l2s_cap_gates_bwd_dw(const float* dh, const float* dh2, const float* dc_in, const float* save, const float* c_prev, const float* P,
@@ -672,6 +707,13 @@ extern "C" int l2s_cap_att_apply_rows(const float* att, const float* dots, float
                                       int R, hipStream_t s) {
   if (!att || !dots || !att_res || rows < 1 || rows > 65535 || row0 < 0 || L < 1 || L > 256 || R < 1 || ld_res < R) return L2S_EINVAL;
   L2S_LAUNCH(cap_att_apply_rows_kernel, dim3(cdiv(R, 64), rows), dim3(256), 0, s, att, dots, att_res, ld_res, row0, count, L, R);
+  return l2s_check_launch();
+}
+extern "C" int l2s_cap_att_apply_groups(const float* att, const float* dots, float* att_res, int ld_res, int rows, int group, int row0,
+                                        const int* count, int L, int R, hipStream_t s) {
+  if (!att || !dots || !att_res || rows < 1 || rows > 65535 || group < 1 || rows % group || row0 < 0 || L < 1 || L > 256 || R < 1 || ld_res < R)
+    return L2S_EINVAL;
+  L2S_LAUNCH(cap_att_apply_groups_kernel, dim3(cdiv(R, 64), rows), dim3(256), 0, s, att, dots, att_res, ld_res, row0, count, group, L, R);
   return l2s_check_launch();
 }
 extern "C" int l2s_pack_rows(float* dst, int ldd, const float* src, int lds, int rows, int cols, hipStream_t s) {

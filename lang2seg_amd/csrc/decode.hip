@@ -5,6 +5,8 @@
 //   l2s_decode_pick_rows       that argmax for every row of a batch of detections (one workgroup per row; the same two device functions, so
 //                              a row decides what l2s_decode_pick decides on it), or the log-probability of a forced token
 //   l2s_decode_beam_step       CaptionModel.py:27-121 beam_step + the completion loop for one t
+//   l2s_decode_beam_step_rows  that step for every detection of a sentence (one workgroup per detection, the same device function)
+//   l2s_decode_beam_finish_rows  CaptionModel.py:123 the final ordering of every detection's completed beams, on the device
 //   l2s_mask_resize_nearest    a predicted canvas at the blob's size, by the rule of the loader's ground-truth masks
 #include "common.h"
 #include "../../include/lang2seg_hip.h"
@@ -161,8 +163,10 @@ __global__ __launch_bounds__(DEC_T) void decode_pick_rows_kernel(const float* lo
   }
 }
 
-// ---------------------------------------------------------------- l2s_decode_beam_step
-__global__ __launch_bounds__(DEC_T) void decode_beam_step_kernel(l2s_beam_step_args a) {
+// ---------------------------------------------------------------- l2s_decode_beam_step, l2s_decode_beam_step_rows
+// one caption's step by a workgroup of DEC_T threads on that caption's slices: the body of both kernels, so a detection of the rows entry
+// decides what the single entry decides on the same logits and tables
+__device__ __forceinline__ void decode_beam_step_body(const l2s_beam_step_args& a) {
 #pragma clang fp contract(off)
   __shared__ float ys[L2S_BEAM_MAX][L2S_BEAM_MAX];
   __shared__ int ix[L2S_BEAM_MAX][L2S_BEAM_MAX];
@@ -276,6 +280,81 @@ __global__ __launch_bounds__(DEC_T) void decode_beam_step_kernel(l2s_beam_step_a
     }
   }
 }
+__global__ __launch_bounds__(DEC_T) void decode_beam_step_kernel(l2s_beam_step_args a) { decode_beam_step_body(a); }
+// one workgroup per detection (rows.h): detection d owns B consecutive rows of the logits and of every state array, and its own tables
+__global__ __launch_bounds__(DEC_T) void decode_beam_step_rows_kernel(l2s_beam_step_args a, int row0, const int* __restrict__ count) {
+  const int d = blockIdx.x;
+  if (!row_live(d, row0, count)) return;
+  const long B = a.B, T = a.T;
+  a.logits += d * B * a.ld_logits;
+  a.beam_seq += d * T * B;
+  a.beam_seq_logprobs += d * T * B;
+  a.beam_logprobs_sum += d * B;
+  a.next_tokens += d * B;
+  a.parents += d * B;
+  a.done += d * B * T * L2S_BEAM_RECORD_WORDS(T);
+  a.done_count += d;
+  for (int j = 0; j < 4; ++j) {
+    if (j >= a.n_state) break;
+    a.state_in[j] += d * B * a.ld_in[j];
+    a.state_out[j] += d * B * a.ld_out[j];
+  }
+  decode_beam_step_body(a);
+}
+
+// ---------------------------------------------------------------- l2s_decode_beam_finish_rows
+// one workgroup per detection: its completed records ordered by p descending, equal p in completion order (CaptionModel.py:123; the rank by
+// counting of the step kernel), the first B written out and the best one once more in the layout of l2s_decode_pick_rows' tables
+__global__ __launch_bounds__(DEC_T) void decode_beam_finish_rows_kernel(const int* __restrict__ done, const int* __restrict__ done_count, int B, int T,
+                                                                        int row0, const int* __restrict__ count, int64_t* beam_seq, float* beam_logps,
+                                                                        float* beam_p, int* beam_n, int64_t* seq, float* logprobs) {
+  __shared__ float ps[L2S_BEAM_MAX * L2S_BEAM_MAX_T];
+  __shared__ int win[L2S_BEAM_MAX];
+  __shared__ int s_first0;
+  const int d = blockIdx.x, tid = threadIdx.x;
+  if (!row_live(d, row0, count)) return;
+  const int RW = L2S_BEAM_RECORD_WORDS(T);
+  const int* recs = done + (long)d * B * T * RW;
+  int n = done_count[d];
+  n = n < 0 ? 0 : (n > B * T ? B * T : n);
+  const int nb = n < B ? n : B;
+  for (int i = tid; i < n; i += DEC_T) ps[i] = __int_as_float(recs[(long)i * RW + 2 * T]);
+  __syncthreads();
+  for (int i = tid; i < n; i += DEC_T) {
+    const float p = ps[i];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) {
+      const float pj = ps[j];
+      rank += (pj > p || (pj == p && j < i)) ? 1 : 0;
+    }
+    if (rank < B) win[rank] = i;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int f = T;
+    if (nb > 0) {
+      const int* rec = recs + (long)win[0] * RW;
+      for (int s = T - 1; s >= 0; --s) f = rec[s] == 0 ? s : f;
+    } else {
+      f = 0;
+    }
+    s_first0 = f;
+    beam_n[d] = nb;
+  }
+  __syncthreads();
+  for (int e = tid; e < B * T; e += DEC_T) {
+    const int v = e / T, s = e % T;
+    const int* rec = v < nb ? recs + (long)win[v] * RW : nullptr;
+    beam_seq[((long)d * B + v) * T + s] = rec ? rec[s] : 0;
+    beam_logps[((long)d * B + v) * T + s] = rec ? __int_as_float(rec[T + s]) : 0.f;
+    if (s == 0) beam_p[(long)d * B + v] = rec ? __int_as_float(rec[2 * T]) : 0.f;
+  }
+  for (int s = tid; s < T; s += DEC_T) {
+    const int* rec = nb > 0 ? recs + (long)win[0] * RW : nullptr;
+    seq[(long)d * T + s] = (rec && s < s_first0) ? rec[s] : 0;
+    logprobs[(long)d * T + s] = (rec && s <= s_first0) ? __int_as_float(rec[T + s]) : 0.f;
+  }
+}
 
 // ---------------------------------------------------------------- l2s_mask_resize_nearest
 __global__ __launch_bounds__(256) void mask_resize_nearest_kernel(const uint8_t* src, int ih, int iw, uint8_t* dst, int H, int W) {
@@ -308,15 +387,35 @@ extern "C" int l2s_decode_pick_rows(const float* logits, int ld_logits, int V1, 
   return l2s_check_launch();
 }
 
-extern "C" int l2s_decode_beam_step(const l2s_beam_step_args* a, hipStream_t s) {
+static bool beam_args_ok(const l2s_beam_step_args* a) {
   if (!a || !a->logits || a->B < 1 || a->B > L2S_BEAM_MAX || a->V1 < a->B || a->ld_logits < a->V1 || a->T < 1 || a->T > L2S_BEAM_MAX_T || a->t < 0 ||
       a->t >= a->T || a->n_state < 0 || a->n_state > 4 || (a->n_state && a->R < 1) || !a->beam_seq || !a->beam_seq_logprobs ||
       !a->beam_logprobs_sum || !a->next_tokens || !a->parents || !a->done || !a->done_count)
-    return L2S_EINVAL;
+    return false;
   for (int j = 0; j < a->n_state; ++j)
-    if (!a->state_in[j] || !a->state_out[j] || a->ld_in[j] < a->R || a->ld_out[j] < a->R) return L2S_EINVAL;
+    if (!a->state_in[j] || !a->state_out[j] || a->ld_in[j] < a->R || a->ld_out[j] < a->R) return false;
+  return true;
+}
+extern "C" int l2s_decode_beam_step(const l2s_beam_step_args* a, hipStream_t s) {
+  if (!beam_args_ok(a)) return L2S_EINVAL;
   const l2s_beam_step_args args = *a;
   L2S_LAUNCH(decode_beam_step_kernel, dim3(1), dim3(DEC_T), 0, s, args);
+  return l2s_check_launch();
+}
+extern "C" int l2s_decode_beam_step_rows(const l2s_beam_step_args* a, int rows, int row0, const int* count, hipStream_t s) {
+  if (!beam_args_ok(a) || rows < 1 || row0 < 0) return L2S_EINVAL;
+  const l2s_beam_step_args args = *a;
+  L2S_LAUNCH(decode_beam_step_rows_kernel, dim3(rows), dim3(DEC_T), 0, s, args, row0, count);
+  return l2s_check_launch();
+}
+extern "C" int l2s_decode_beam_finish_rows(const int* done, const int* done_count, int B, int T, int rows, int row0, const int* count,
+                                           int64_t* beam_seq, float* beam_logps, float* beam_p, int* beam_n, int64_t* seq, float* logprobs,
+                                           hipStream_t s) {
+  if (!done || !done_count || B < 1 || B > L2S_BEAM_MAX || T < 1 || T > L2S_BEAM_MAX_T || rows < 1 || row0 < 0 || !beam_seq || !beam_logps ||
+      !beam_p || !beam_n || !seq || !logprobs)
+    return L2S_EINVAL;
+  L2S_LAUNCH(decode_beam_finish_rows_kernel, dim3(rows), dim3(DEC_T), 0, s, done, done_count, B, T, row0, count, beam_seq, beam_logps, beam_p,
+             beam_n, seq, logprobs);
   return l2s_check_launch();
 }
 

@@ -79,22 +79,27 @@ def detect_sentence(net, s, scale, ih, iw, max_per_image, thresh, cap, rec=None,
 class _RowsStage(object):
     """the caption branch on rows behind a sentence's detections.  tokens: per sentence the expression's ids (its nonzero labels)"""
 
-    def __init__(self, net, tokens, describe, expr_score, ix_to_word=None):
+    def __init__(self, net, tokens, describe, expr_score, ix_to_word=None, beam_size=1):
         from ..nets import caption_rows, decode
         caption_rows.check_features(net)                          # ValueErrors that name the variant, before any launch
-        decode.check_args(net, 1, 1, 1.0)
+        decode.check_args(net, 1, beam_size if describe else 1, 1.0)
         self.net, self.tokens, self.describe, self.expr_score, self.ix_to_word = net, tokens, bool(describe), bool(expr_score), ix_to_word
+        self.beam_size = int(beam_size) if describe else 1         # > 1: beam search on rows; 1: the greedy launches
 
     def one(self, i):
         """the stage of sentence i alone (its re-run)"""
-        return _RowsStage(self.net, [self.tokens[i]], self.describe, self.expr_score, self.ix_to_word)
+        return _RowsStage(self.net, [self.tokens[i]], self.describe, self.expr_score, self.ix_to_word, self.beam_size)
 
     def run(self, i, canvases, cap, ih, iw, written):
         """-> the sentence's results as device copies (the network's row buffers are the next sentence's too)"""
         net = self.net
         att, fc = net.caption_features_rows(canvases, cap, (ih, iw), count=written)
         out = {}
-        if self.describe:
+        if self.describe and self.beam_size > 1:
+            r = net.caption_beam_rows(att, fc, rows=cap, count=written, beam_size=self.beam_size)
+            out.update(seq=r['seq'].clone(), lp=r['logprobs'].clone(), bseq=r['beam_seq'].clone(), blp=r['beam_logprobs'].clone(),
+                       bp=r['beam_p'].clone(), bn=r['beam_n'].clone())
+        elif self.describe:
             r = net.caption_decode_rows(att, fc, rows=cap, count=written)
             out['seq'], out['lp'] = r['seq'].clone(), r['logprobs'].clone()
         if self.expr_score:
@@ -103,7 +108,8 @@ class _RowsStage(object):
             self.net_score = r['score']                            # the network's buffer: the judge stage reads it in stream order
         return out
 
-    KEYS = (('seq', np.int64), ('lp', np.float32), ('elp', np.float32), ('score', np.float32))
+    KEYS = (('seq', np.int64), ('lp', np.float32), ('bseq', np.int64), ('blp', np.float32), ('bp', np.float32), ('bn', np.int32),
+            ('elp', np.float32), ('score', np.float32))
 
     def read_back(self, outs):
         """one copy for all sentences -> per sentence {key: array}"""
@@ -124,6 +130,9 @@ class _RowsStage(object):
             n = int(np.argmax(s == 0)) if (s == 0).any() else s.size
             p['caption_tokens'] = [int(v) for v in s[:n]]
             p['caption_logprobs'] = [float(v) for v in h['lp'][k, :n]]
+            if 'bn' in h:                                          # beam search: every beam, best first, as caption_image writes them
+                p['caption_beams'] = [dict(seq=[int(v) for v in h['bseq'][k, j]], logps=[float(v) for v in h['blp'][k, j]], p=float(h['bp'][k, j]))
+                                      for j in range(int(h['bn'][k]))]
             if self.ix_to_word is not None:
                 from .caption_device import decode_sequence
                 p['caption'] = decode_sequence(self.ix_to_word, p['caption_tokens'])
@@ -322,12 +331,12 @@ class _Detector(object):
         return res
 
 
-def rows_stage(net, labels, describe, expr_score, ix_to_word=None):
+def rows_stage(net, labels, describe, expr_score, ix_to_word=None, beam_size=1):
     """the stage detect_image / eval_split_device run behind every sentence, or None without the options.  ValueError on a network whose
     caption branch pools no mask (the variant is named)"""
     if not describe and not expr_score:
         return None
-    return _RowsStage(net, [[int(w) for w in row if w != 0] for row in np.asarray(labels)], describe, expr_score, ix_to_word)
+    return _RowsStage(net, [[int(w) for w in row if w != 0] for row in np.asarray(labels)], describe, expr_score, ix_to_word, beam_size)
 
 
 def judge_stage(net, labels, gt_masks, gt_boxes, scale, judge, rerank, per_token, expr_score):
@@ -342,13 +351,14 @@ def judge_stage(net, labels, gt_masks, gt_boxes, scale, judge, rerank, per_token
 
 
 def detect_image(net, data, labels, max_per_image=100, thresh=0.0, _cap=None, _pool_words=None, _capture=None, describe=False, expr_score=False,
-                 ix_to_word=None, gt_masks=None, gt_boxes=None, rerank=None, per_token=False, selection=None):
+                 ix_to_word=None, gt_masks=None, gt_boxes=None, rerank=None, per_token=False, selection=None, beam_size=1):
     """data: {'data': float32 (1, H, W, 3) blob, 'im_info': [H, W, scale]} (+ 'file_name'); labels: int [S][T] token ids, zero padded.
     -> one list per sentence of dicts, class ascending and inside a class score descending: file_name, sent_index, roi (the proposal's
     row), category_id, box [x1, y1, x2, y2] (original image), score and (networks with a mask branch) area and segmentation
     {'size': [ih, iw], 'counts': COCO RLE string}.  max_per_image <= 0: no limit; ties at the limit all stay.
     describe (network 'cycle'): also what the captioner says about each detection's mask, greedy: caption_tokens, caption_logprobs and, with
-    ix_to_word ({str(id): word}), caption.  expr_score: also how well each detection's mask explains the sentence: expr_logprobs, the
+    ix_to_word ({str(id): word}), caption.  beam_size > 1 (with describe): beam search on rows instead (Network.caption_beam_rows): the three
+    fields are the best beam's, and caption_beams lists every beam, best first, as [{seq, logps, p}].  expr_score: also how well each detection's mask explains the sentence: expr_logprobs, the
     teacher-forced log-probabilities of the sentence's n tokens and the end token under that mask (n + 1 values), and expr_logprob, their
     sum.  Both run on the device behind each sentence (nets/caption_rows.py) and cost one more read-back per image.
     gt_masks (uint8 [S][Hs][Ws]) with gt_boxes ([S][4], x1 y1 x2 y2 in the scaled image): every detection is judged against its sentence's
@@ -365,7 +375,7 @@ def detect_image(net, data, labels, max_per_image=100, thresh=0.0, _cap=None, _p
     if ((labels != 0).sum(1) == 0).any():
         raise ValueError('labels: every sentence needs at least one token')
     S = int(labels.shape[0])
-    stage = rows_stage(net, labels, describe, expr_score, ix_to_word)
+    stage = rows_stage(net, labels, describe, expr_score, ix_to_word, beam_size)
     if (gt_masks is None) != (gt_boxes is None):
         raise ValueError('gt_masks and gt_boxes come together')
     if gt_masks is None and (rerank or per_token or selection is not None):

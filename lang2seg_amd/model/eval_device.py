@@ -156,7 +156,8 @@ def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1, detect=
     if detect is not None:
         from .detect_device import _Detector
         from .detect_device import rows_stage
-        stage = rows_stage(net, np.asarray(data['labels'])[:n_sent], detect.get('describe'), detect.get('expr_score'), detect.get('ix_to_word'))
+        stage = rows_stage(net, np.asarray(data['labels'])[:n_sent], detect.get('describe'), detect.get('expr_score'), detect.get('ix_to_word'),
+                           detect.get('beam_size', 1))
         judge = None
         if detect.get('judge') or detect.get('rerank') or detect.get('per_token'):
             from .detect_device import judge_stage
@@ -258,7 +259,7 @@ def check_judge_options(detections, judge, rerank, per_token, expr_score, varian
 
 
 def _run(loader, model, split, opt, rank, world, details, with_masks, progress, predictions=None, pool_words=None, detections=None,
-         describe=False, expr_score=False, judge=False, rerank=None, per_token=False, selection=None, selection_totals=None):
+         describe=False, expr_score=False, judge=False, rerank=None, per_token=False, selection=None, selection_totals=None, beam_size=1):
     if (describe or expr_score) and detections is None:
         raise ValueError('describe / expr_score (--describe, --expr_score) add fields to the detections: they need detections (--dump_detections)')
     lambdas = check_judge_options(detections is not None, judge, rerank, per_token, expr_score, None if with_masks else 'vgg')
@@ -293,7 +294,8 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
                 n = min(n, num_sents - issued)
             rec = O.eval_records(n, device)
             dopt = None if detections is None else dict(max_per_image=opt.get('max_per_image', 100), thresh=opt.get('det_thresh', 0.0),
-                                                        describe=describe, expr_score=expr_score, ix_to_word=getattr(loader, 'ix_to_word', None))
+                                                        describe=describe, expr_score=expr_score, ix_to_word=getattr(loader, 'ix_to_word', None),
+                                                        beam_size=beam_size)
             if judging:
                 dopt.update(judge=True, rerank=lambdas, per_token=per_token)
             if dopt is None:
@@ -346,7 +348,8 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
 
 
 def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=None, predictions=None, _pool_words=None, detections=None,
-                      describe=False, expr_score=False, judge=False, rerank=None, per_token=False, selection=None, selection_totals=None):
+                      describe=False, expr_score=False, judge=False, rerank=None, per_token=False, selection=None, selection_totals=None,
+                      beam_size=1):
     """model/test.py eval_split on the device.  Returns its 7-tuple (acc, eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U,
     num_sent).  details: a list that receives (pred_roi, pred_class, pred_box, hit, I, U) per sentence of this rank.
     predictions: a list that receives one dict per sentence of this rank: file_name, sent_index (position in the image's test batch),
@@ -354,7 +357,8 @@ def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=
     detections: a list that receives every detection of every sentence of this rank (model/detect_device.py detect_image's dicts, flat;
     opt['max_per_image'] (100) and opt['det_thresh'] (0.0) are its limits).  Metrics and predictions do not depend on it.
     describe / expr_score: detect_image's options for those detections (the captioner on every detection; the expression's log-likelihood
-    under every detection's mask); they need `detections` and the cycle network.
+    under every detection's mask); they need `detections` and the cycle network.  beam_size > 1 with describe: beam search on rows, the
+    detections gain caption_beams.
     judge / rerank (a list of lambdas; implies judge) / per_token: detect_image's judging of every detection against the sentence's ground
     truth (I, U, hit per detection) and its rules; they need `detections`, rerank needs expr_score.  selection: a list that receives
     per sentence of this rank {file_name, sent_index, gt_area, rules: {rule: {det, category_id, hit, I, U, key}}}; selection_totals: a dict
@@ -367,7 +371,7 @@ def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=
             split, b['it_pos_now'], b['it_max'], t.acc * 100.0 / max(t.loss_evals, 1), t.seg_correct[0] * 100.0 / max(t.seg_total, 1),
             t.cum_I * 100.0 / max(t.cum_U, 1)))
     t = _run(loader, model, split, opt, rank, world, details, True, progress, predictions, _pool_words, detections, describe, expr_score,
-             judge, rerank, per_token, selection, selection_totals)
+             judge, rerank, per_token, selection, selection_totals, beam_size)
     return t.acc / t.loss_evals, EVAL_SEG_IOU_LIST, t.seg_correct, t.seg_total, t.cum_I, t.cum_U, t.num_sent
 
 

@@ -158,8 +158,8 @@ def caption_decode_rows(net, att_feats, fc_feats=None, rows=None, count=None, sa
     """greedy decoding of `rows` masks at once -> {'seq': int64 [rows][seq_length], 'logprobs': f32 [rows][seq_length]} on the device, zero
     from a row's first 0 on and in the rows at or beyond count[0]; no read-back on the batched route"""
     if not sample_max or beam_size != 1:
-        raise ValueError('--sample_max %r --beam_size %r: decoding on rows is greedy (--sample_max 1 --beam_size 1); sampled and beam decoding '
-                         'take one mask at a time (caption_decode)' % (sample_max, beam_size))
+        raise ValueError('--sample_max %r --beam_size %r: caption_decode_rows is greedy (--sample_max 1 --beam_size 1); beam search on rows is '
+                         'caption_beam_rows, sampled decoding takes one mask at a time (caption_decode)' % (sample_max, beam_size))
     rows, att, fc = _start(net, 'caption_decode_rows', att_feats, fc_feats, att_feats.shape[0] if rows is None else rows, count)
     T = int(net.opt['seq_length'])
     seq, lps, score, fin = _outputs(net, rows, T)
@@ -186,3 +186,95 @@ def caption_score_rows(net, att_feats, fc_feats, tokens, rows=None, count=None):
     else:
         _run_loop(net, att, fc, rows, count, T, seq, lps, score, fin, io[1])
     return {'logprobs': lps, 'score': score}
+
+
+# ------------------------------------------------------------------ beam search on rows
+def _beam_outputs(net, rows, T, B):
+    """seq int64 [rows][T] | beam_seq int64 [rows][B][T] | logprobs f32 [rows][T] | beam_logprobs f32 [rows][B][T] | beam_p f32 [rows][B] |
+    beam_n int32 [rows] in one zeroed buffer: a dead row reads as an empty sentence with no beams"""
+    n8, n4 = rows * T * (1 + B), rows * T * (1 + B) + rows * B + rows
+    out = net.buf('rows.beam_out', (8 * n8 + 4 * n4,), torch.uint8, zero=True)
+    w8, w4 = out[:8 * n8].view(i64), out[8 * n8:].view(f32)
+    o = [rows * T, rows * T * (1 + B), rows * T * (1 + B) + rows * B]
+    return {'seq': w8[:rows * T].view(rows, T), 'beam_seq': w8[rows * T:].view(rows, B, T), 'logprobs': w4[:o[0]].view(rows, T),
+            'beam_logprobs': w4[o[0]:o[1]].view(rows, B, T), 'beam_p': w4[o[1]:o[2]].view(rows, B), 'beam_n': w4[o[2]:].view(i32)}
+
+
+def _beam_tables(net, nb, T, B):
+    """a chunk's tables of CaptionModel.beam_search, per detection what nets/decode.py keeps for one caption"""
+    RW = O.beam_record_words(T)
+    ib = lambda n, shp, dt: net.buf('rows.beam.' + n, shp, dt)
+    return dict(seq=ib('seq', (nb, T, B), i32), lp=ib('lp', (nb, T, B), f32), sum=ib('sum', (nb, B), f32), parents=ib('parents', (nb, B), i32),
+                done=ib('done', (nb, B * T * RW), i32), cnt=ib('cnt', (nb,), i32))
+
+
+def _beam_finish(out, tb, B, T, n, c0, count):
+    O.decode_beam_finish_rows(tb['done'], tb['cnt'], B, T, n, out['beam_seq'][c0:], out['beam_logprobs'][c0:], out['beam_p'][c0:], out['beam_n'][c0:],
+                              out['seq'][c0:], out['logprobs'][c0:], count, c0)
+
+
+def _beam_batched(net, att, fc, rows, count, T, B, out):
+    """per chunk of n detections: the head on n rows, then per token the captioner's step on n * B state rows in groups of B (a group shares
+    its detection's head), the logits on n * B rows and the beam step on n detections, which gathers `new` back into `cur`; the final
+    ordering once per chunk.  Nothing depends on `count`, nothing comes back"""
+    cap = net.captioner
+    R, V1 = net.opt['rnn_size'], net.opt['vocab_size'] + 1
+    nb = min(rows, CHUNK)
+    b = lambda n, shp, zero=False: net.buf('rows.' + n, shp, f32, zero)
+    logits = b('logits', (nb * B, V1))
+    tokens = net.buf('rows.tokens', (nb * B,), i64)
+    tb = _beam_tables(net, nb, T, B)
+    for c0 in range(0, rows, CHUNK):
+        n = min(CHUNK, rows - c0)
+        H = cap.rows_head(b, att[c0:c0 + n], fc[c0:c0 + n] if fc is not None else None, n, nb)
+        cur, new = cap.rows_states(b, nb * B)
+        O.memset_zero(tokens)
+        for t in range(T):
+            o = cap.rows_step(b, H, cur, new, n * B, nb * B, tokens, None, count, c0, group=B)
+            O.linear_fwd(o, cap.pv('logit.weight'), cap.pv('logit.bias'), logits, n * B, V1, R)
+            O.decode_beam_step_rows(logits, V1, B, t, T, n, tb['seq'], tb['lp'], tb['sum'], cap.rows_gather(new, cur), R, tokens, tb['parents'],
+                                    tb['done'], tb['cnt'], count, c0)
+        _beam_finish(out, tb, B, T, n, c0, count)
+
+
+def _beam_loop(net, att, fc, rows, count, T, B, out):
+    """per live detection the single-mask launches of nets/decode.py's beam search, the beam step on that detection's slices of the chunk's
+    tables; the final ordering once per chunk that has a live detection; the one read-back of `count`"""
+    cap = net.captioner
+    R, V1 = net.opt['rnn_size'], net.opt['vocab_size'] + 1
+    live = rows if count is None else max(0, min(rows, int(count[0:1].cpu()[0])))
+    nb = min(rows, CHUNK)
+    tb = _beam_tables(net, nb, T, B)
+    tokens = net.buf('dec.tokens', (B,), i64)
+    for c0 in range(0, live, CHUNK):
+        n = min(CHUNK, live - c0)
+        for k in range(n):
+            r = c0 + k
+            ad, patt = decode._head(net, att[r])
+            H = cap.decode_start(ad, patt, decode._fc_checked(net, fc[r]) if cap.reads_fc else None)
+            O.memset_zero(tokens)
+            cur, new = cap.new_states('a', B), cap.new_states('b', B)
+            for t in range(T):
+                logits = decode.step(net, H, cur, new, tokens, B)
+                O.decode_beam_step(logits, V1, B, t, T, tb['seq'][k], tb['lp'][k], tb['sum'][k],
+                                   [(new[s][0], cur[s][0], new[s][1], cur[s][1]) for s in cap.states], R, tokens, tb['parents'][k], tb['done'][k],
+                                   tb['cnt'][k:k + 1])
+        _beam_finish(out, tb, B, T, n, c0, None)
+
+
+def caption_beam_rows(net, att_feats, fc_feats=None, rows=None, count=None, beam_size=3):
+    """beam search (CaptionModel.beam_search, as caption_decode(beam_size=) runs it for one mask) for `rows` masks at once -> on the device
+    {'seq': int64 [rows][seq_length] and 'logprobs': f32 [rows][seq_length], the best beam in caption_decode_rows' layout;
+     'beam_seq': int64 [rows][beam_size][seq_length], 'beam_logprobs': f32 likewise, 'beam_p': f32 [rows][beam_size], best first;
+     'beam_n': int32 [rows], the beams a row has}; zeros in the rows at or beyond count[0].  No read-back on the batched route"""
+    decode.check_args(net, 1, beam_size, 1.0)                   # the --beam_size errors of the single-mask path, before anything else
+    T, B = int(net.opt['seq_length']), int(beam_size)
+    if T > O.BEAM_MAX_T:                                        # (check_args lets one beam pass: the greedy single-mask path has no tables)
+        raise ValueError('--beam_size %r with seq_length %d: beam search keeps at most %d tokens' % (beam_size, T, O.BEAM_MAX_T))
+    rows, att, fc = _start(net, 'caption_beam_rows', att_feats, fc_feats, att_feats.shape[0] if rows is None else rows, count)
+    out = _beam_outputs(net, rows, T, B)
+    if batched(net):
+        _beam_batched(net, att, fc, rows, count, T, B, out)
+    else:
+        _beam_loop(net, att, fc, rows, count, T, B, out)
+    return out

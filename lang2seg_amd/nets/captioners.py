@@ -187,8 +187,17 @@ class Captioner(object):
     # ------------------------------------------------------------------ the caption branch on rows (nets/caption_rows.py: the batched route)
     # b(name, shape, zero=False): the route's float buffers ('rows.*'), sized for nb rows; n <= nb rows of the chunk are in use.  A captioner
     # that serves the route has rows_forced (teacher forcing: the token-only work of the T inputs, once per call -> what rows_step takes as
-    # pre_t, per t), rows_head (per chunk), rows_states (two zeroed sets) and rows_step (one token: cur -> new, returns the outputs
-    # [nb][rnn_size]); the number of entries each issues depends neither on n nor on count[0].
+    # pre_t, per t), rows_head (per chunk), rows_states (two zeroed sets), rows_step (one token: cur -> new, returns the outputs
+    # [nb][rnn_size]) and rows_gather (beam search: the state arrays of set `src` as (in, out, ld_in, ld_out) into set `dst`); the number
+    # of entries each issues depends neither on n nor on count[0].  Beam search calls rows_step with group = beam_size: n and nb then count
+    # STATE rows, `group` consecutive ones per row of the head, and the row entries are their *_groups forms (on_rows).
+    @staticmethod
+    def on_rows(name, group, head, n, *tail, **kw):
+        """ops.<name>_rows(*head, n, *tail), or with group > 1 ops.<name>_groups(*head, n, group, *tail): one call site for both"""
+        if group == 1:
+            return getattr(O, name + '_rows')(*head, n, *tail, **kw)
+        return getattr(O, name + '_groups')(*head, n, group, *tail, **kw)
+
     def rows_ok(self):
         """the batched route serves this captioner at the network's shapes (otherwise: the loop)"""
         return False
@@ -360,7 +369,11 @@ class Att2in2(Captioner):
         R = self.net.opt['rnn_size']
         return [(b('h.' + k, (nb, R), True), b('c.' + k, (nb, R), True)) for k in 'ab']
 
-    def rows_step(self, b, H, cur, new, n, nb, tokens, pre_t, count, row0):
+    def rows_gather(self, src, dst):
+        R = self.net.opt['rnn_size']
+        return [(src[0], dst[0], R, R), (src[1], dst[1], R, R)]
+
+    def rows_step(self, b, H, cur, new, n, nb, tokens, pre_t, count, row0, group=1):
         R, IE, AH = self.dims()
         pv = self.pv
         sums, att_h, dots = b('sums', (nb, 5 * R)), b('att_h', (nb, AH)), b('dots', (nb, 256))
@@ -373,8 +386,9 @@ class Att2in2(Captioner):
             self.token_inputs(xt, sums, n)
             O.linear_fwd(h0, pv('core.h2h.weight'), pv('core.h2h.bias'), sums, n, 5 * R, R, accumulate=True)
         O.linear_fwd(h0, pv('core.attention.h2att.weight'), pv('core.attention.h2att.bias'), att_h, n, AH, R)
-        O.cap_att_dots_rows(H['patt'], att_h, pv('core.attention.alpha_net.weight'), pv('core.attention.alpha_net.bias'), n, L, AH, dots, count, row0)
-        O.cap_apply_gates_rows(H['Pm'], dots, pv('core.a2c.bias'), sums, cp, c1, h1, n, L, R, count, row0)
+        self.on_rows('cap_att_dots', group, (H['patt'], att_h, pv('core.attention.alpha_net.weight'), pv('core.attention.alpha_net.bias')), n, L, AH,
+                     dots, count, row0)
+        self.on_rows('cap_apply_gates', group, (H['Pm'], dots, pv('core.a2c.bias'), sums, cp, c1, h1), n, L, R, count, row0)
         return h1
 
 
@@ -556,7 +570,11 @@ class TopDown(Captioner):
         st = b('td_state', (2, 5 * nb * R), True)
         return [dict(zip(('hl', 'cl', 'ca', 'lin'), s.split([nb * R, nb * R, nb * R, 2 * nb * R]))) for s in st]
 
-    def rows_step(self, b, H, cur, new, n, nb, tokens, pre_t, count, row0):
+    def rows_gather(self, src, dst):
+        R = self.net.opt['rnn_size']
+        return [(src[k], dst[k], R, R) for k in ('hl', 'cl', 'ca')] + [(src['lin'][R:], dst['lin'][R:], 2 * R, 2 * R)]
+
+    def rows_step(self, b, H, cur, new, n, nb, tokens, pre_t, count, row0, group=1):
         R, IE, AH = self.dims()
         Ka = IE + 2 * R
         pv = self.pv
@@ -570,13 +588,13 @@ class TopDown(Captioner):
             self.token_inputs(xt, xpre, n)
         lin0, lin1 = cur['lin'], new['lin']
         h_att = lin1[R:]
-        O.lstm_cell_rows(xpre, None, None, [(cur['hl'], R, wa_ih, Ka, R), (lin0[R:], 2 * R, wa_hh, R, R)], cur['ca'], new['ca'], h_att, n, R, count, row0,
-                         ld_pre=ld_pre, pre2=H['fcrow'], ld_h=2 * R)
+        self.on_rows('lstm_cell', group, (xpre, None, None, [(cur['hl'], R, wa_ih, Ka, R), (lin0[R:], 2 * R, wa_hh, R, R)], cur['ca'], new['ca'], h_att),
+                     n, R, count, row0, ld_pre=ld_pre, pre2=H['fcrow'], ld_h=2 * R)
         O.linear_fwd(h_att, h2w, h2b, att_h, n, AH, R, ldx=2 * R)
-        O.cap_att_dots_rows(H['patt'], att_h, aw, ab, n, L, AH, dots, count, row0)
-        O.cap_att_apply_rows(H['a'], dots, lin1, n, L, R, count, row0, ld_res=2 * R)
-        O.lstm_cell_rows(None, bl_ih, bl_hh, [(lin1, 2 * R, wl_ih, 2 * R, 2 * R), (cur['hl'], R, wl_hh, R, R)], cur['cl'], new['cl'], new['hl'], n, R,
-                         count, row0)
+        self.on_rows('cap_att_dots', group, (H['patt'], att_h, aw, ab), n, L, AH, dots, count, row0)
+        self.on_rows('cap_att_apply', group, (H['a'], dots, lin1), n, L, R, count, row0, ld_res=2 * R)
+        self.on_rows('lstm_cell', group, (None, bl_ih, bl_hh, [(lin1, 2 * R, wl_ih, 2 * R, 2 * R), (cur['hl'], R, wl_hh, R, R)], cur['cl'], new['cl'],
+                                         new['hl']), n, R, count, row0)
         return new['hl']
 
 

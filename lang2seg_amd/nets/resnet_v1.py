@@ -1133,6 +1133,11 @@ class resnetv1(Network):
         """greedy decoding of `rows` masks at once -> device tensors {'seq' int64 [rows][seq_length], 'logprobs' f32 [rows][seq_length]}"""
         return caption_rows.caption_decode_rows(self, att_feats, fc_feats, rows, count, sample_max, beam_size)
 
+    def caption_beam_rows(self, att_feats, fc_feats=None, rows=None, count=None, beam_size=3):
+        """beam search for `rows` masks at once, on the device (nets/caption_rows.py): the best beam as caption_decode_rows returns it, and
+        all beam_size beams of every row, best first"""
+        return caption_rows.caption_beam_rows(self, att_feats, fc_feats, rows, count, beam_size)
+
     def caption_score_rows(self, att_feats, fc_feats, tokens, rows=None, count=None):
         """the teacher-forced log-likelihood of one expression (ints 1 .. vocab_size, length n) under `rows` masks -> device tensors
         {'logprobs' f32 [rows][n + 1], 'score' f32 [rows]}"""

@@ -845,22 +845,31 @@ def decode_beam_step(logits, V1, B, t, T, beam_seq, beam_seq_logprobs, beam_logp
     """beam_step + the completion loop of CaptionModel.beam_search for one t.  logits f32 [B][V1]; beam_seq int32 [T][B], beam_seq_logprobs
     f32 [T][B], beam_logprobs_sum f32 [B]; states: up to four (in, out, ld_in, ld_out) of B rows of R floats, gathered by parent; next_tokens
     int64 [B], parents int32 [B]; done int32 [B * T][2 T + 2] (seq | logps | p | completion index), done_count int32 [1]"""
+    a = _beam_args('decode_beam_step', 1, logits, V1, B, t, T, beam_seq, beam_seq_logprobs, beam_logprobs_sum, states, R, next_tokens, parents, done,
+                   done_count, ld_logits)
+    call('l2s_decode_beam_step', C.byref(a), stream())
+
+
+def _beam_args(name, rows, logits, V1, B, t, T, beam_seq, beam_seq_logprobs, beam_logprobs_sum, states, R, next_tokens, parents, done, done_count,
+               ld_logits):
+    """the checked argument block of the beam step for `rows` captions (the single entry: 1)"""
     if not 1 <= B <= BEAM_MAX:
         raise ValueError('--beam_size %r: 1 .. %d' % (B, BEAM_MAX))
     ld = V1 if ld_logits is None else ld_logits
-    if (logits.numel() < (B - 1) * ld + V1 or beam_seq.numel() < T * B or beam_seq_logprobs.numel() < T * B or beam_logprobs_sum.numel() < B or
-            next_tokens.numel() < B or parents.numel() < B or done.numel() < B * T * beam_record_words(T) or done_count.numel() < 1):
-        raise ValueError('decode_beam_step: a buffer is smaller than B = %d, T = %d, V1 = %d ask' % (B, T, V1))
+    n = rows * B
+    if (logits.numel() < (n - 1) * ld + V1 or beam_seq.numel() < T * n or beam_seq_logprobs.numel() < T * n or beam_logprobs_sum.numel() < n or
+            next_tokens.numel() < n or parents.numel() < n or done.numel() < n * T * beam_record_words(T) or done_count.numel() < rows):
+        raise ValueError('%s: a buffer is smaller than B = %d, T = %d, V1 = %d ask' % (name, B, T, V1))
     a = _lib.BeamStepArgs()
     a.logits, a.ld_logits, a.V1, a.B, a.t, a.T, a.R, a.n_state = ptr(logits), int(ld), int(V1), int(B), int(t), int(T), int(R), len(states)
     a.beam_seq, a.beam_seq_logprobs, a.beam_logprobs_sum = ptr(beam_seq), ptr(beam_seq_logprobs), ptr(beam_logprobs_sum)
     assert len(states) <= 4
     for j, (si, so, li, lo) in enumerate(states):
-        if si.numel() < B * R or so.numel() < B * R or li < R or lo < R:
-            raise ValueError('decode_beam_step: state %d is smaller than B = %d rows of R = %d' % (j, B, R))
+        if si.numel() < n * R or so.numel() < n * R or li < R or lo < R:     # (a strided [n][R] view counts its own elements only)
+            raise ValueError('%s: state %d is smaller than B = %d rows of R = %d' % (name, j, B, R))
         a.state_in[j], a.state_out[j], a.ld_in[j], a.ld_out[j] = ptr(si), ptr(so), int(li), int(lo)
     a.next_tokens, a.parents, a.done, a.done_count = ptr(next_tokens), ptr(parents), ptr(done), ptr(done_count)
-    call('l2s_decode_beam_step', C.byref(a), stream())
+    return a
 
 
 def mask_resize_nearest(src, ih, iw, dst, H, W):
@@ -921,23 +930,29 @@ def lstm_cell_rows(pre, add0, add1, segs, c_prev, c, h, rows, R, count=None, row
     and h[r * ld_h].  ld_pre = 0: one row of pre for all rows.  Up to two segments; None entries are skipped.  Every tensor is the flat
     view that starts at its first element (h inside a wider row: array.view(-1)[offset:])."""
     _rows_count('lstm_cell_rows', rows, row0, count)
+    a = _lstm_rows_args('lstm_cell_rows', pre, add0, add1, segs, c_prev, c, h, rows, R, ld_pre, pre2, ld_pre2, ld_c_prev, ld_c, ld_h, rows)
+    call('l2s_lstm_cell_rows', C.byref(a), int(R), int(rows), int(row0), ptr(count), stream())
+
+
+def _lstm_rows_args(name, pre, add0, add1, segs, c_prev, c, h, rows, R, ld_pre, pre2, ld_pre2, ld_c_prev, ld_c, ld_h, rows_pre2):
+    """the checked argument block of the cell on rows; rows_pre2: the rows of pre2 (a detection's row under lstm_cell_groups)"""
     G = 4 * R
     ld_pre, ld_pre2 = (G if v is None else int(v) for v in (ld_pre, ld_pre2))
     ld_c_prev, ld_c, ld_h = (R if v is None else int(v) for v in (ld_c_prev, ld_c, ld_h))
     span = lambda ld, w: (rows - 1) * ld + w
     segs = [sg for sg in segs if sg is not None]
     if len(segs) > 2 or R < 1 or min(ld_c_prev, ld_c, ld_h) < R or \
-            any(p is not None and (0 < ld < G or ld < 0 or p.numel() < span(ld, G)) for p, ld in ((pre, ld_pre), (pre2, ld_pre2))) or \
+            any(p is not None and (0 < ld < G or ld < 0 or p.numel() < (n - 1) * ld + G) for p, ld, n in ((pre, ld_pre, rows), (pre2, ld_pre2, rows_pre2))) or \
             any(v is not None and v.numel() < G for v in (add0, add1)) or \
             c_prev.numel() < span(ld_c_prev, R) or c.numel() < span(ld_c, R) or h.numel() < span(ld_h, R) or \
             any(n < 1 or ld < n or ldx < n or x.numel() < span(ldx, n) or w.numel() < (G - 1) * ld + n for x, ldx, w, ld, n in segs):
-        raise ValueError('lstm_cell_rows: a buffer is smaller than rows = %d, R = %d and its leading dimension ask, or more than two segments' % (rows, R))
+        raise ValueError('%s: a buffer is smaller than rows = %d, R = %d and its leading dimension ask, or more than two segments' % (name, rows, R))
     a = _lib.LstmRows()
     a.pre, a.ld_pre, a.pre2, a.ld_pre2, a.add0, a.add1 = ptr(pre), ld_pre, ptr(pre2), ld_pre2, ptr(add0), ptr(add1)
     a.c_prev, a.ld_c_prev, a.c, a.ld_c, a.h, a.ld_h = ptr(c_prev), ld_c_prev, ptr(c), ld_c, ptr(h), ld_h
     for q, (x, ldx, w, ld, n) in zip(a.seg, segs):
         q.x, q.ldx, q.w, q.ld, q.n = ptr(x), int(ldx), ptr(w), int(ld), int(n)
-    call('l2s_lstm_cell_rows', C.byref(a), int(R), int(rows), int(row0), ptr(count), stream())
+    return a
 
 
 def cap_att_apply_rows(att, dots, att_res, rows, L, R, count=None, row0=0, ld_res=None):
@@ -961,6 +976,84 @@ def decode_pick_rows(logits, V1, rows, t, T, finished, seq, logprobs, next_token
         raise ValueError('decode_pick_rows: a buffer is smaller than rows = %d / V1 = %d / t = %d of T = %d ask, or has the wrong dtype' % (rows, V1, t, T))
     call('l2s_decode_pick_rows', ptr(logits), int(ld), int(V1), int(rows), int(row0), ptr(count), int(t), int(T), ptr(forced), ptr(finished), ptr(seq),
          ptr(logprobs), ptr(next_token), ptr(score), stream())
+
+
+# ---- beam search on rows: `rows` detections with B beam rows each (group = B consecutive state rows per detection)
+def decode_beam_step_rows(logits, V1, B, t, T, rows, beam_seq, beam_seq_logprobs, beam_logprobs_sum, states, R, next_tokens, parents, done,
+                          done_count, count=None, row0=0, ld_logits=None):
+    """decode_beam_step for every live detection in one launch: logits f32 [rows * B][V1]; beam_seq int32 [rows][T][B], beam_seq_logprobs f32
+    [rows][T][B], beam_logprobs_sum f32 [rows][B]; states: up to four (in, out, ld_in, ld_out) of rows * B rows of R floats, gathered by
+    parent inside each detection's B rows; next_tokens int64 [rows * B], parents int32 [rows][B]; done int32 [rows][B * T][2 T + 2],
+    done_count int32 [rows]"""
+    _rows_count('decode_beam_step_rows', rows, row0, count)
+    a = _beam_args('decode_beam_step_rows', int(rows), logits, V1, B, t, T, beam_seq, beam_seq_logprobs, beam_logprobs_sum, states, R, next_tokens,
+                   parents, done, done_count, ld_logits)
+    if next_tokens.dtype != torch.int64:
+        raise ValueError('decode_beam_step_rows: next_tokens is int64')
+    call('l2s_decode_beam_step_rows', C.byref(a), int(rows), int(row0), ptr(count), stream())
+
+
+def decode_beam_finish_rows(done, done_count, B, T, rows, beam_seq, beam_logps, beam_p, beam_n, seq, logprobs, count=None, row0=0):
+    """the final ordering of every live detection's completed beams (p descending, completion order among equals): beam_seq int64
+    [rows][B][T], beam_logps f32 [rows][B][T], beam_p f32 [rows][B], beam_n int32 [rows], and the best beam as seq int64 [rows][T] /
+    logprobs f32 [rows][T] in decode_pick_rows' layout"""
+    _rows_count('decode_beam_finish_rows', rows, row0, count)
+    if not 1 <= B <= BEAM_MAX or not 1 <= T <= BEAM_MAX_T:
+        raise ValueError('--beam_size %r: 1 .. %d, with at most %d tokens (got %r)' % (B, BEAM_MAX, BEAM_MAX_T, T))
+    n = rows * B
+    if (done.numel() < n * T * beam_record_words(T) or done_count.numel() < rows or min(beam_seq.numel(), beam_logps.numel()) < n * T or
+            beam_p.numel() < n or beam_n.numel() < rows or min(seq.numel(), logprobs.numel()) < rows * T or beam_seq.dtype != torch.int64 or
+            seq.dtype != torch.int64 or beam_n.dtype != torch.int32 or done.dtype != torch.int32 or done_count.dtype != torch.int32):
+        raise ValueError('decode_beam_finish_rows: a buffer is smaller than rows = %d, B = %d, T = %d ask, or has the wrong dtype' % (rows, B, T))
+    call('l2s_decode_beam_finish_rows', ptr(done), ptr(done_count), int(B), int(T), int(rows), int(row0), ptr(count), ptr(beam_seq), ptr(beam_logps),
+         ptr(beam_p), ptr(beam_n), ptr(seq), ptr(logprobs), stream())
+
+
+def _groups(name, rows, group, row0, count):
+    _rows_count(name, rows, row0, count)
+    if isinstance(group, bool) or group < 1 or rows % group:
+        raise ValueError('%s: rows = %r is no multiple of group = %r' % (name, rows, group))
+    return rows // group
+
+
+def cap_att_dots_groups(patt, att_h, aw, ab, rows, group, L, D, dots, count=None, row0=0, ld_att_h=None):
+    """cap_att_dots_rows on `rows` state rows of which `group` consecutive ones share a detection's patt [rows / group][L][D]"""
+    dets = _groups('cap_att_dots_groups', rows, group, row0, count)
+    ld = D if ld_att_h is None else int(ld_att_h)
+    if patt.numel() < dets * L * D or dots.numel() < rows * 256 or L > 256 or ld < D or att_h.numel() < (rows - 1) * ld + D:
+        raise ValueError('cap_att_dots_groups: a buffer is smaller than rows = %d in groups of %d ask, or L = %d > 256' % (rows, group, L))
+    call('l2s_cap_att_dots_groups', ptr(patt), ptr(att_h), ld, ptr(aw), ptr(ab), int(rows), int(group), int(row0), ptr(count), L, D, ptr(dots),
+         stream())
+
+
+def cap_apply_gates_groups(P, dots, b_a2c, sums, c_prev, c, h, rows, group, L, R, count=None, row0=0, ld_sums=None):
+    """cap_apply_gates_rows on `rows` state rows of which `group` consecutive ones share a detection's P [rows / group][L][2R]"""
+    dets = _groups('cap_apply_gates_groups', rows, group, row0, count)
+    ld = 5 * R if ld_sums is None else int(ld_sums)
+    if P.numel() < dets * L * 2 * R or dots.numel() < rows * 256 or min(c_prev.numel(), c.numel(), h.numel()) < rows * R or L > 256 or R > 1024 or \
+            ld < 5 * R or sums.numel() < (rows - 1) * ld + 5 * R:
+        raise ValueError('cap_apply_gates_groups: a buffer is smaller than rows = %d in groups of %d ask, or L = %d > 256, or R = %d > 1024'
+                         % (rows, group, L, R))
+    call('l2s_cap_apply_gates_groups', ptr(P), ptr(dots), ptr(b_a2c), ptr(sums), ld, ptr(c_prev), ptr(c), ptr(h), int(rows), int(group), int(row0),
+         ptr(count), L, R, stream())
+
+
+def cap_att_apply_groups(att, dots, att_res, rows, group, L, R, count=None, row0=0, ld_res=None):
+    """cap_att_apply_rows on `rows` state rows of which `group` consecutive ones share a detection's att [rows / group][L][R]"""
+    dets = _groups('cap_att_apply_groups', rows, group, row0, count)
+    ld = R if ld_res is None else int(ld_res)
+    if att.numel() < dets * L * R or dots.numel() < rows * 256 or L > 256 or ld < R or att_res.numel() < (rows - 1) * ld + R:
+        raise ValueError('cap_att_apply_groups: a buffer is smaller than rows = %d in groups of %d ask, or L = %d > 256' % (rows, group, L))
+    call('l2s_cap_att_apply_groups', ptr(att), ptr(dots), ptr(att_res), ld, int(rows), int(group), int(row0), ptr(count), L, R, stream())
+
+
+def lstm_cell_groups(pre, add0, add1, segs, c_prev, c, h, rows, group, R, count=None, row0=0, ld_pre=None, pre2=None, ld_pre2=None, ld_c_prev=None,
+                     ld_c=None, ld_h=None):
+    """lstm_cell_rows on `rows` state rows of which `group` consecutive ones belong to one detection: pre2 [rows / group][ld_pre2] is the
+    per-detection term, read at row r // group; everything else is per state row"""
+    dets = _groups('lstm_cell_groups', rows, group, row0, count)
+    a = _lstm_rows_args('lstm_cell_groups', pre, add0, add1, segs, c_prev, c, h, rows, R, ld_pre, pre2, ld_pre2, ld_c_prev, ld_c, ld_h, dets)
+    call('l2s_lstm_cell_groups', C.byref(a), int(R), int(rows), int(group), int(row0), ptr(count), stream())
 
 
 def rcnn_predict(heads, ldh, R, ncls, stds4, means4, cls_prob, bbox_pred):

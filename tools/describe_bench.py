@@ -8,7 +8,9 @@ by HIP events.  Three paths, timed in turn inside one process, `reps` rounds, th
     loop      the same entry points with net.rows_batched = False: the single-mask launches row by row
     per_mask  what the tree offered before: per mask l2s_mask_resize_nearest + caption_features(mask) + caption_decode (one read-back each);
               it has no score, so it is the yardstick of both
-Each timing includes the features.  --cells 1 adds `cells`: one nn.LSTMCell step of the top-down attention cell at
+Each timing includes the features.  --beam_size B > 1 times beam search instead (and no scoring): `beam_batched` and `beam_loop` are
+caption_features_rows + caption_beam_rows by the two routes, `per_mask_beam` is what the tree offered before for the same job,
+caption_decode(beam_size=B) mask by mask on the same masks (one read-back each).  --cells 1 adds `cells`: one nn.LSTMCell step of the top-down attention cell at
 rnn_size = input_encoding_size = 512 on 1, 8 and 64 rows, as l2s_lstm_cell_rows, as the existing launches it stands for on rows (two
 l2s_linear_fwd + l2s_lstm_cell_fwd per row) and as l2s_topdown_cell_fwd per row; per path the time of CELL_CALLS steps issued back to
 back between two events, over CELL_CALLS (where a kernel is shorter than the host takes to issue it, that is the issue rate).
@@ -83,6 +85,7 @@ def main():
     ap.add_argument('--dtype', default='bf16'); ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--counts', default='1,8,64'); ap.add_argument('--out', default=None, help='also write the JSON result to this file')
     ap.add_argument('--caption_model', default='att2in2', choices=['att2in2', 'topdown'])
+    ap.add_argument('--beam_size', type=int, default=1, help='> 1: time beam search on rows against caption_decode(beam_size=) mask by mask')
     ap.add_argument('--cells', type=int, default=0, help='1: also time one LSTMCell step on rows three ways (see above)')
     a = ap.parse_args()
     from lang2seg_amd import ops as O
@@ -120,11 +123,15 @@ def main():
     big = torch.empty((H, W), dtype=torch.uint8, device='cuda')
     res = dict(metric='describe_us_per_sentence', dtype=a.dtype, caption_model=net.cap_model, seq_length=T, expression_tokens=len(expr),
                canvas=[ih, iw], blob=[H, W], map=list(s['net_conv_hw']), reps=a.reps, rows={})
+    if a.beam_size > 1:
+        res['beam_size'] = a.beam_size
 
     def rows_path(cap, cnt, batched, score):
         net.rows_batched = batched
         att, fc = net.caption_features_rows(masks[:cap], cap, (ih, iw), count=cnt)
-        if score:
+        if a.beam_size > 1:
+            net.caption_beam_rows(att, fc, rows=cap, count=cnt, beam_size=a.beam_size)
+        elif score:
             net.caption_score_rows(att, fc, expr, rows=cap, count=cnt)
         else:
             net.caption_decode_rows(att, fc, rows=cap, count=cnt)
@@ -134,7 +141,7 @@ def main():
         for k in range(n):
             O.mask_resize_nearest(masks[k], ih, iw, big, H, W)
             att, fc = net.caption_features(big)
-            net.caption_decode(att, fc)
+            net.caption_decode(att, fc, beam_size=a.beam_size)
 
     cases = [(64, int(c)) for c in a.counts.split(',')] + [(128, 1)]
     for cap, n in cases:
@@ -142,6 +149,8 @@ def main():
         paths = {'describe_batched': lambda: rows_path(cap, cnt, True, False), 'describe_loop': lambda: rows_path(cap, cnt, False, False),
                  'score_batched': lambda: rows_path(cap, cnt, True, True), 'score_loop': lambda: rows_path(cap, cnt, False, True),
                  'per_mask': lambda: per_mask(n)}
+        if a.beam_size > 1:
+            paths = {'beam_batched': paths['describe_batched'], 'beam_loop': paths['describe_loop'], 'per_mask_beam': paths['per_mask']}
         if cap == 128:
             paths = {k: v for k, v in paths.items() if k.endswith('batched')}
         times = {k: [] for k in paths}

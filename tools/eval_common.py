@@ -34,6 +34,8 @@ def parse_args(argv=None):
     p.add_argument('--det_thresh', type=float, default=0.0, help='--dump_detections: a detection needs a score above this')
     p.add_argument('--describe', type=int, default=0, help='--dump_detections on the cycle network: also what the captioner says about every '
                    'detection (caption_tokens, caption_logprobs, caption; greedy)')
+    p.add_argument('--beam_size', type=int, default=1, help='--describe 1: beam search with this many beams instead of greedy decoding; every '
+                   'detection also gets caption_beams, best first')
     p.add_argument('--expr_score', type=int, default=0, help='--dump_detections on the cycle network: also the log-likelihood of the sentence '
                    'under every detection\'s mask (expr_logprob, expr_logprobs)')
     p.add_argument('--judge_detections', type=int, default=0, help='--dump_detections on a network with masks: also judge every detection against '
@@ -121,6 +123,9 @@ def main(args, variant):
     for k in ('describe', 'expr_score'):
         if args.get(k) and not args.get('dump_detections'):
             raise ValueError('--%s 1 needs --dump_detections PATH: it adds fields to every detection (--%s, --dump_detections)' % (k, k))
+    if args.get('beam_size', 1) > 1 and not args.get('describe'):
+        raise ValueError('--beam_size %d without --describe 1: the beams are those of the captions of every detection (--beam_size, --describe)'
+                         % args['beam_size'])
     if (args.get('describe') or args.get('expr_score')) and variant == 'vgg':
         raise ValueError('--describe / --expr_score: --variant vgg has no caption branch (the cycle network has one)')
     judge, lambdas, per_token = selection_options(args, variant)
@@ -189,7 +194,8 @@ def main(args, variant):
         sel, sel_tot = ([], {}) if judge else (None, None)
         kw = dict(judge=True, rerank=lambdas, per_token=per_token, selection=sel, selection_totals=sel_tot) if judge else {}
         res = eval_split_device(loader, net, None, split, eopt, rank=rank, world=world, predictions=preds, detections=dets,
-                                describe=bool(args.get('describe')), expr_score=bool(args.get('expr_score')), **kw)
+                                describe=bool(args.get('describe')), expr_score=bool(args.get('expr_score')),
+                                beam_size=args.get('beam_size', 1) if args.get('describe') else 1, **kw)
         dump_predictions(args, preds, rank, world)
         dump_predictions(args, dets, rank, world, 'dump_detections', 'detections')
         if args.get('dump_selection'):

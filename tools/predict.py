@@ -7,7 +7,8 @@ each mask as DIR/<image>_<sent_index>.png, decoded on the device from the run le
     --all_detections 1 [--max_per_image N] [--det_thresh T]: every instance the network finds for each sentence instead of its first
 pick (model/detect_device.py: class-wise NMS with cfg.TEST.NMS, the best N over all classes); prints one list per sentence, --png writes
 DIR/<image>_<sent_index>_<k>.png.  With it, --describe 1 adds what the captioner says about EVERY detection (caption_tokens,
-caption_logprobs, caption; greedy) and --expr_score 1 how well every detection's mask explains the sentence (expr_logprob: the
+caption_logprobs, caption; greedy, or with --beam_size B > 1 by beam search on all detections at once, which also lists every beam as
+caption_beams, best first) and --expr_score 1 how well every detection's mask explains the sentence (expr_logprob: the
 teacher-forced log-likelihood of the sentence under that mask, expr_logprobs: per token and the end token); both need --variant cycle
 (nets/caption_rows.py) and either without --all_detections 1 is an error.
     --caption 1 [--beam_size B] [--sample_max 0|1] [--temperature t]: also what the captioner says about each predicted mask
@@ -123,7 +124,7 @@ def main(args):
         if args.get('describe'):
             words = {str(i): 'w%d' % i for i in range(1, loader.vocab_size + 1)} if args['synthetic'] else loader.ix_to_word
         dets = detect_image(net, data, labels, max_per_image=args['max_per_image'], thresh=args['det_thresh'], describe=bool(args.get('describe')),
-                            expr_score=bool(args.get('expr_score')), ix_to_word=words)
+                            expr_score=bool(args.get('expr_score')), ix_to_word=words, beam_size=args['beam_size'] if args.get('describe') else 1)
         if args['png']:
             os.makedirs(args['png'], exist_ok=True)
             for lst in dets:
