@@ -717,6 +717,14 @@ int l2s_cap_apply_gates_rows(const float* P, const float* dots, const float* b_a
  * log-probabilities so far (set at t == 0, then added to in the order of t). */
 int l2s_decode_pick_rows(const float* logits, int ld_logits, int V1, int rows, int row0, const int* count, int t, int T, const int64_t* forced,
                          int* finished, int64_t* seq, float* logprobs, int64_t* next_token, float* sum, hipStream_t s);
+/* One workgroup per row: teacher forcing with a token row per row (AttModel.forward + LanguageModelCriterion for a batch of different
+ * sentences), step t of T.  targets int64 [rows][T]: row r holds w_1 .. w_n, 0, then padding; lengths int32 [rows]: the scored positions
+ * n_r + 1 of row r, 1 <= lengths[r] <= T.  A live row with t < lengths[r] gets logprobs[r][t] = logits[r][targets[r][t]] - logsumexp of
+ * its V1 logits (l2s_decode_pick_rows' forced arithmetic: the same bits for the same logits and token; a token outside the table is
+ * clamped), that value added to `sum` f32 [rows] where given (set at t == 0), and next_token[r] = targets[r][t].  With t >= lengths[r]
+ * logprobs and sum are not written (the caller's zeros stay) and next_token[r] = 0.  Dead rows are neither read nor written. */
+int l2s_decode_force_rows(const float* logits, int ld_logits, int V1, int rows, int row0, const int* count, int t, int T, const int64_t* targets,
+                          const int* lengths, float* logprobs, int64_t* next_token, float* sum, hipStream_t s);
 /* The top-down step on rows.  l2s_lstm_cell_rows: one nn.LSTMCell step (gate order i, f, g, o; l2s_topdown_cell_fwd's arithmetic) for every
  * live row in one launch:
  *   gates[r][4R] = pre[r * ld_pre] + pre2[r * ld_pre2] + add0 + add1 + sum over up to two segments w_k[4R][:n_k] . x_k[r * ldx_k][:n_k]

@@ -230,6 +230,7 @@ SIGS = {
     'l2s_cap_att_dots_rows': (i32, [vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]),
     'l2s_cap_apply_gates_rows': (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, i32, vp]),
     'l2s_decode_pick_rows': (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    'l2s_decode_force_rows': (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
     'l2s_lstm_cell_rows': (i32, [C.POINTER(LstmRows), i32, i32, i32, vp, vp]),
     'l2s_cap_att_apply_rows': (i32, [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp]),
     'l2s_decode_beam_step_rows': (i32, [C.POINTER(BeamStepArgs), i32, i32, vp, vp]),

@@ -4,6 +4,8 @@
 //   l2s_decode_pick            AttModel.py:172-201    argmax or inverse-CDF draw of one row, the finished flag, the next input token
 //   l2s_decode_pick_rows       that argmax for every row of a batch of detections (one workgroup per row; the same two device functions, so
 //                              a row decides what l2s_decode_pick decides on it), or the log-probability of a forced token
+//   l2s_decode_force_rows      teacher forcing with a token row and a length per row: AttModel.forward + LanguageModelCriterion's gather
+//                              and mask for a batch of different sentences, one step per launch
 //   l2s_decode_beam_step       CaptionModel.py:27-121 beam_step + the completion loop for one t
 //   l2s_decode_beam_step_rows  that step for every detection of a sentence (one workgroup per detection, the same device function)
 //   l2s_decode_beam_finish_rows  CaptionModel.py:123 the final ordering of every detection's completed beams, on the device
@@ -51,6 +53,13 @@ __device__ __forceinline__ void row_max_logsum(const float* x, int V1, float* re
   for (int k = tid; k < V1; k += DEC_T) s += expf(x[k] - m);
   s = block_sum(s, red);
   ls = logf(s);
+}
+// a teacher-forced token as an index of that row (a token outside the table: clamped, never an address) and its log-probability: what
+// l2s_decode_pick_rows' forced branch and l2s_decode_force_rows both write, so equal logits and tokens give equal bits
+__device__ __forceinline__ int forced_index(int64_t f, int V1) { return f < 0 ? 0 : (f >= V1 ? V1 - 1 : (int)f); }
+__device__ __forceinline__ float row_logprob(const float* x, int k, float m, float ls) {
+#pragma clang fp contract(off)
+  return (x[k] - m) - ls;
 }
 // the greedy pick of that workgroup: the best word of each thread, of each wave, then of the four waves in order (wv, wk: 4 each).  The
 // result is the same in every thread; all NaN: no candidate, word 0
@@ -145,8 +154,7 @@ __global__ __launch_bounds__(DEC_T) void decode_pick_rows_kernel(const float* lo
   row_max_logsum(x, V1, red, m, ls);
   int pick = 0;
   if (forced) {
-    const int64_t f = *forced;
-    pick = f < 0 ? 0 : (f >= V1 ? V1 - 1 : (int)f);      // (a token outside the table: clamped, never an address)
+    pick = forced_index(*forced, V1);
   } else {
     pick = block_argmax(x, V1, m, ls, wv, wk);
   }
@@ -155,11 +163,35 @@ __global__ __launch_bounds__(DEC_T) void decode_pick_rows_kernel(const float* lo
     const int fin = (forced || t == 0) ? 0 : finished[r];
     const int tok = fin ? 0 : pick;
     seq[(long)r * T + t] = tok;
-    const float lp = fin ? 0.f : (x[pick] - m) - ls;
+    const float lp = fin ? 0.f : row_logprob(x, pick, m, ls);
     logprobs[(long)r * T + t] = lp;
     if (sum) sum[r] = t == 0 ? lp : sum[r] + lp;           // the row's joint log-probability, added up left to right
     next_token[r] = tok;
     finished[r] = fin | (tok == 0);
+  }
+}
+// one workgroup per live row: teacher forcing with the row's own token and length.  Step t of a row with t < lengths[r] scores
+// targets[r][t]; behind its length a row writes nothing but a valid next input
+__global__ __launch_bounds__(DEC_T) void decode_force_rows_kernel(const float* logits, int ld, int V1, int row0, const int* __restrict__ count, int t, int T,
+                                                                  const int64_t* __restrict__ targets, const int* __restrict__ lengths, float* logprobs,
+                                                                  int64_t* next_token, float* sum) {
+#pragma clang fp contract(off)
+  __shared__ float red[4];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  if (!row_live(r, row0, count)) return;
+  if (t >= lengths[r]) {                                   // (the same in every thread of the workgroup)
+    if (tid == 0) next_token[r] = 0;
+    return;
+  }
+  const float* x = logits + (long)r * ld;
+  float m, ls;
+  row_max_logsum(x, V1, red, m, ls);
+  if (tid == 0) {
+    const int pick = forced_index(targets[(long)r * T + t], V1);
+    const float lp = row_logprob(x, pick, m, ls);
+    logprobs[(long)r * T + t] = lp;
+    if (sum) sum[r] = t == 0 ? lp : sum[r] + lp;           // the row's joint log-probability, added up left to right
+    next_token[r] = pick;
   }
 }
 
@@ -384,6 +416,13 @@ extern "C" int l2s_decode_pick_rows(const float* logits, int ld_logits, int V1, 
   if (!logits || V1 < 1 || ld_logits < V1 || rows < 1 || row0 < 0 || t < 0 || t >= T || !finished || !seq || !logprobs || !next_token) return L2S_EINVAL;
   L2S_LAUNCH(decode_pick_rows_kernel, dim3(rows), dim3(DEC_T), 0, s, logits, ld_logits, V1, row0, count, t, T, forced, finished, seq, logprobs,
              next_token, sum);
+  return l2s_check_launch();
+}
+extern "C" int l2s_decode_force_rows(const float* logits, int ld_logits, int V1, int rows, int row0, const int* count, int t, int T,
+                                     const int64_t* targets, const int* lengths, float* logprobs, int64_t* next_token, float* sum, hipStream_t s) {
+  if (!logits || V1 < 1 || ld_logits < V1 || rows < 1 || row0 < 0 || t < 0 || t >= T || !targets || !lengths || !logprobs || !next_token) return L2S_EINVAL;
+  L2S_LAUNCH(decode_force_rows_kernel, dim3(rows), dim3(DEC_T), 0, s, logits, ld_logits, V1, row0, count, t, T, targets, lengths, logprobs, next_token,
+             sum);
   return l2s_check_launch();
 }
 

@@ -131,14 +131,18 @@ class _Export(object):
         return out
 
 
-def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1, detect=None, caption=None):
+def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1, detect=None, caption=None, speaker=None):
     """every sentence of one image through the device path; record base + i for sentence i.  No host synchronisation.
     pool_words >= 0 or None: also keep the predictions on the device (None: the default pool budget) -> the image's _Export.
     detect: None, or a dict (max_per_image, thresh) that asks for every detection of each sentence too (model/detect_device.py) and
     receives 'detector' (the image's _Detector) and 'sentence' (forward_test_sentence of sentence i again, for its re-runs)
     caption: None, or a callable (i, the sentence's outputs, the image's _Export) run behind sentence i's mask, while the sentence's
-    buffers are still its own (model/caption_device.py)"""
+    buffers are still its own (model/caption_device.py)
+    speaker: None, or the image's model/caption_eval.py ImageStage: it receives the ground-truth masks on the device and runs behind
+    sentence i's mask as `caption` does"""
     img, lab_d, lens, box_d, gm = _upload_image(net, data, n_sent)
+    if speaker is not None:
+        speaker.gm = gm
     im_info = np.asarray(data['im_info'], dtype=np.float32).reshape(-1)[:3]
     scale, ih, iw = _geometry(im_info)
     d = dict(data=img, im_info=im_info, S=1)
@@ -180,6 +184,8 @@ def _eval_image(net, data, n_sent, rec, base, with_masks, pool_words=-1, detect=
                 ex.encode(i)
         if caption is not None:
             caption(i, s, ex)
+        if speaker is not None:
+            speaker.caption(i, s, ex)
         if det is not None:                                   # last: its mask head pass reuses the heads' buffers
             det.run(i, s)
     return ex
@@ -259,7 +265,16 @@ def check_judge_options(detections, judge, rerank, per_token, expr_score, varian
 
 
 def _run(loader, model, split, opt, rank, world, details, with_masks, progress, predictions=None, pool_words=None, detections=None,
-         describe=False, expr_score=False, judge=False, rerank=None, per_token=False, selection=None, selection_totals=None, beam_size=1):
+         describe=False, expr_score=False, judge=False, rerank=None, per_token=False, selection=None, selection_totals=None, beam_size=1,
+         caption_eval=False, caption_describe=False, caption_totals=None):
+    if (caption_describe or caption_totals is not None) and not caption_eval:
+        raise ValueError('caption_describe / caption_totals (--caption_eval_describe) belong to the speaker\'s evaluation: they need '
+                         'caption_eval (--caption_eval 1)')
+    ctot = None
+    if caption_eval:
+        from .caption_eval import CaptionTotals, ImageStage, check_variant
+        check_variant(model)                                    # names the variant, before anything runs
+        ctot = CaptionTotals()
     if (describe or expr_score) and detections is None:
         raise ValueError('describe / expr_score (--describe, --expr_score) add fields to the detections: they need detections (--dump_detections)')
     lambdas = check_judge_options(detections is not None, judge, rerank, per_token, expr_score, None if with_masks else 'vgg')
@@ -298,7 +313,11 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
                                                         beam_size=beam_size)
             if judging:
                 dopt.update(judge=True, rerank=lambdas, per_token=per_token)
-            if dopt is None:
+            if caption_eval:
+                speaker = ImageStage(model, np.asarray(data['labels'])[:n], None, caption_describe, beam_size,
+                                     opt.get('ix_to_word') or getattr(loader, 'ix_to_word', None))
+                ex = _eval_image(model, data, n, rec, 0, with_masks, -1 if predictions is None else pool_words, detect=dopt, speaker=speaker)
+            elif dopt is None:
                 ex = _eval_image(model, data, n, rec, 0, with_masks, -1 if predictions is None else pool_words)
             else:
                 ex = _eval_image(model, data, n, rec, 0, with_masks, -1 if predictions is None else pool_words, detect=dopt)
@@ -308,6 +327,12 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
                 rec_h = rec.cpu()
                 predictions.extend(ex.collect(rec_h, data.get('file_name')))
                 chunks[-1] = rec_h
+            if caption_eval:                                   # one more read-back per image: every sentence's log-probabilities at once
+                cf = speaker.fields()
+                speaker.add_to(ctot, cf)
+                if predictions is not None:
+                    for p, q in zip(predictions[len(predictions) - n:], cf):
+                        p.update(q)
             if dopt is not None:                               # one read-back per image; a sentence that did not fit its buffers runs again
                 extra = dict(image_id=data['image_id']) if 'image_id' in data else None
                 n_sel = len(sel) if judging else 0
@@ -342,6 +367,14 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
         w = 4 + len(EVAL_SEG_IOU_LIST)
         for k, t in enumerate(rule_tot.values()):
             t.set_ints(v[len(base) + k * w:len(base) + (k + 1) * w])
+        if caption_eval:                                       # the speaker's float64 sums: one all_reduce of their own
+            cv = torch.from_numpy(ctot.vector())
+            if dist.get_backend() != 'gloo':
+                cv = cv.to(device)
+            dist.all_reduce(cv, op=dist.ReduceOp.SUM)
+            ctot.set_vector(cv.cpu().numpy())
+    if caption_totals is not None:
+        caption_totals.update(ctot.as_dict())
     if selection_totals is not None:
         selection_totals.update((name, t.as_dict()) for name, t in rule_tot.items())
     return tot
@@ -349,7 +382,7 @@ def _run(loader, model, split, opt, rank, world, details, with_masks, progress, 
 
 def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=None, predictions=None, _pool_words=None, detections=None,
                       describe=False, expr_score=False, judge=False, rerank=None, per_token=False, selection=None, selection_totals=None,
-                      beam_size=1):
+                      beam_size=1, caption_eval=False, caption_describe=False, caption_totals=None):
     """model/test.py eval_split on the device.  Returns its 7-tuple (acc, eval_seg_iou_list, seg_correct, seg_total, cum_I, cum_U,
     num_sent).  details: a list that receives (pred_roi, pred_class, pred_box, hit, I, U) per sentence of this rank.
     predictions: a list that receives one dict per sentence of this rank: file_name, sent_index (position in the image's test batch),
@@ -364,6 +397,12 @@ def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=
     per sentence of this rank {file_name, sent_index, gt_area, rules: {rule: {det, category_id, hit, I, U, key}}}; selection_totals: a dict
     that receives per rule {acc, num_sent, seg_correct (at EVAL_SEG_IOU_LIST), cum_I, cum_U}, summed over the ranks.  Without them the
     launches and every returned bit are what they are without these options.
+    caption_eval: the speaker's evaluation (model/caption_eval.py; cycle and cycle_response): every sentence's own expression, cut to
+    seq_length tokens, scored teacher-forced under its ground-truth mask.  The predictions gain gt_expr_logprob and gt_expr_logprobs
+    (n + 1 values); with caption_describe also gt_caption_tokens, gt_caption_logprobs, gt_caption_exact (greedy, or the best of beam_size
+    beams) and gt_caption, the words, where opt['ix_to_word'] or the loader's ix_to_word names them.  caption_totals: a dict that receives num_sent, num_tok, loss (minus the sum of all log-probabilities over
+    num_tok), perplexity, loss_per_image (the mean over images of LanguageModelCriterion on the image's sentences) and exact_match,
+    summed over the ranks in float64.  Without caption_eval the launches are what they are without it.
     (_pool_words: the run-length pool of an image in words instead of its default budget; checks of the host fallback.)"""
     def progress(data, t):
         b = data['bounds']
@@ -371,7 +410,7 @@ def eval_split_device(loader, model, crit, split, opt, rank=0, world=1, details=
             split, b['it_pos_now'], b['it_max'], t.acc * 100.0 / max(t.loss_evals, 1), t.seg_correct[0] * 100.0 / max(t.seg_total, 1),
             t.cum_I * 100.0 / max(t.cum_U, 1)))
     t = _run(loader, model, split, opt, rank, world, details, True, progress, predictions, _pool_words, detections, describe, expr_score,
-             judge, rerank, per_token, selection, selection_totals, beam_size)
+             judge, rerank, per_token, selection, selection_totals, beam_size, caption_eval, caption_describe, caption_totals)
     return t.acc / t.loss_evals, EVAL_SEG_IOU_LIST, t.seg_correct, t.seg_total, t.cum_I, t.cum_U, t.num_sent
 
 

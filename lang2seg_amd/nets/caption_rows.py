@@ -20,6 +20,12 @@ Two routes:
             by row (head, decode_start, T x step), the decision by l2s_decode_pick_rows on one row.  Reads `count` back once per call.
             Slow (about rows * 3 T dependent launches, 5 T for topdown) but correct for every captioner, and the cross-check of the batched route.
 
+caption_score_pairs scores row r's OWN expression (its own length) under row r's mask: the evaluation of the speaker on a split.  Its
+batched route drives the captioner's rows_step the greedy way - the step's input is the token l2s_decode_force_rows left for the row, the
+row's own target of the step before - so rows_step takes nothing new and the launches per token are the greedy ones with the new kernel in
+place of the pick: att2in2 8, topdown 9, whatever `rows`, `count` and the lengths are (every chunk runs Tmax + 1 steps; a row behind its
+length is fed 0 and writes nothing).  Its loop route is the single-mask launches row by row with the new kernel on one row.
+
 Rows are processed in chunks of at most CHUNK = 64, so the head's products (a, patt, P: 196 * 64 rows of 4 rnn_size + att_hid_size floats;
 topdown has no P) stay near 0.1 GB at the production widths beside the chunk's 0.1 GB of features.  Every buffer is `rows.*` (the loop also uses decoding's
 `dec.*`): a call between a training forward and its backward leaves what that backward reads alone.  The results are the network's buffers:
@@ -186,6 +192,125 @@ def caption_score_rows(net, att_feats, fc_feats, tokens, rows=None, count=None):
     else:
         _run_loop(net, att, fc, rows, count, T, seq, lps, score, fin, io[1])
     return {'logprobs': lps, 'score': score}
+
+
+# ------------------------------------------------------------------ one expression per row
+def _pairs_tokens(net, tokens, lengths, rows):
+    """the checked targets of caption_score_pairs -> (targets int64 [rows][Tmax + 1]: w_1 .. w_n, 0, zeros; ntok int32 [rows] = n + 1;
+    Tmax + 1), both on the device.  Host tokens are checked here in full; device tokens (int64) are not read back: the kernel clamps a
+    token outside the table, and a length outside 1 .. Tmax is cut to that range"""
+    V = int(net.opt['vocab_size']) if getattr(net, 'opt', None) else 0
+    on_device = isinstance(tokens, torch.Tensor) and tokens.device.type != 'cpu'
+    if on_device:
+        if tokens.dtype != i64 or tokens.dim() != 2 or tokens.shape[0] < 1 or tokens.shape[1] < 1:
+            raise ValueError('caption_score_pairs: tokens on the device is int64 [rows][Tmax], got %s %s' % (tokens.dtype, tuple(tokens.shape)))
+        R, Tmax = int(tokens.shape[0]), int(tokens.shape[1])
+    else:
+        tok = np.asarray(tokens.numpy() if isinstance(tokens, torch.Tensor) else tokens)
+        if tok.ndim != 2 or tok.shape[0] < 1 or tok.shape[1] < 1 or tok.dtype.kind not in 'iu':
+            raise ValueError('caption_score_pairs: tokens is an int array [rows][Tmax], got %s %s' % (tok.dtype, tok.shape))
+        tok = tok.astype(np.int64)
+        R, Tmax = int(tok.shape[0]), int(tok.shape[1])
+    if rows is not None and int(rows) != R:
+        raise ValueError('caption_score_pairs: tokens has %d rows, rows = %r' % (R, rows))
+    if isinstance(lengths, torch.Tensor) and lengths.device.type != 'cpu':
+        if lengths.dtype != i32 or lengths.numel() != R:
+            raise ValueError('caption_score_pairs: lengths on the device is int32 [rows = %d], got %s %s' % (R, lengths.dtype, tuple(lengths.shape)))
+        if not on_device:
+            raise ValueError('caption_score_pairs: lengths on the device goes with tokens on the device; host tokens take host lengths')
+        n_d = lengths.view(-1)
+    elif lengths is not None or not on_device:
+        if lengths is None:
+            n = (tok != 0).sum(1)
+        else:
+            n = np.asarray(lengths.numpy() if isinstance(lengths, torch.Tensor) else lengths)
+            if n.shape != (R,) or n.dtype.kind not in 'iu':
+                raise ValueError('caption_score_pairs: lengths is one int per row [rows = %d], got %s %s' % (R, n.dtype, n.shape))
+        n = n.astype(np.int64)
+        if n.min() < 1:
+            raise ValueError('caption_score_pairs: tokens / lengths: row %d is empty, every row needs at least one token' % int(np.argmin(n)))
+        if n.max() > Tmax:
+            raise ValueError('caption_score_pairs: lengths: row %d has %d tokens, tokens holds Tmax = %d' % (int(np.argmax(n)), int(n.max()), Tmax))
+        n_d = None
+    else:
+        n_d = (tokens != 0).sum(1).to(i32)
+    T = Tmax + 1
+    if not on_device:
+        inside = np.arange(Tmax)[None, :] < n[:, None]
+        bad = inside & ((tok < 1) | (tok > V))
+        if bad.any():
+            r = int(np.argmax(bad.any(1)))
+            raise ValueError('caption_score_pairs: tokens are ints 1 .. vocab_size = %d inside a row\'s length; row %d is %r' % (V, r, tok[r, :n[r]].tolist()[:8]))
+        tgt = np.zeros((R, T), np.int64)
+        tgt[:, :Tmax] = np.where(inside, tok, 0)
+        dev = torch.device(net.device)
+        return torch.from_numpy(tgt).to(dev), torch.from_numpy((n + 1).astype(np.int32)).to(dev), T
+    if n_d is None:
+        n_d = torch.from_numpy(n.astype(np.int32)).to(tokens.device)
+    n_d = n_d.clamp(1, Tmax)
+    tgt = torch.zeros((R, T), dtype=i64, device=tokens.device)
+    tgt[:, :Tmax] = torch.where(torch.arange(Tmax, device=tokens.device)[None, :] < n_d[:, None], tokens, torch.zeros_like(tokens))
+    return tgt, (n_d + 1).to(i32), T
+
+
+def _pairs_batched(net, att, fc, rows, count, T, targets, ntok, lps, score):
+    """per chunk: the head, then per token the captioner's step driven the greedy way (its input is the token the kernel left in
+    `tokens`: the row's own target of the step before), the logits and l2s_decode_force_rows.  Nothing depends on `count` or `rows`"""
+    cap = net.captioner
+    R, V1 = net.opt['rnn_size'], net.opt['vocab_size'] + 1
+    nb = min(rows, CHUNK)
+    b = lambda n, shp, zero=False: net.buf('rows.' + n, shp, f32, zero)
+    logits = b('logits', (nb, V1))
+    tokens = net.buf('rows.tokens', (nb,), i64)
+    for c0 in range(0, rows, CHUNK):
+        n = min(CHUNK, rows - c0)
+        H = cap.rows_head(b, att[c0:c0 + n], fc[c0:c0 + n] if fc is not None else None, n, nb)
+        st = cap.rows_states(b, nb)
+        O.memset_zero(tokens)                                   # <bos>; a dead row's slot stays a valid index for the embedding
+        for t in range(T):
+            out = cap.rows_step(b, H, st[t & 1], st[1 - (t & 1)], n, nb, tokens, None, count, c0)
+            O.linear_fwd(out, cap.pv('logit.weight'), cap.pv('logit.bias'), logits, n, V1, R)
+            O.decode_force_rows(logits, V1, n, t, T, targets[c0:], ntok[c0:], lps[c0:], tokens, count, c0, score=score[c0:])
+
+
+def _pairs_loop(net, att, fc, rows, count, T, targets, ntok, lps, score):
+    """the single-mask launches row by row, the new kernel on one row; the one read-back of `count`.  Every row runs its T steps: behind
+    its length the kernel feeds 0 and writes nothing"""
+    cap = net.captioner
+    V1 = net.opt['vocab_size'] + 1
+    n = rows if count is None else max(0, min(rows, int(count[0:1].cpu()[0])))
+    tokens = net.buf('rows.token', (1,), i64)
+    for r in range(n):
+        ad, patt = decode._head(net, att[r])
+        H = cap.decode_start(ad, patt, decode._fc_checked(net, fc[r]) if cap.reads_fc else None)
+        O.memset_zero(tokens)
+        cur, new = cap.new_states('a', 1), cap.new_states('b', 1)
+        for t in range(T):
+            logits = decode.step(net, H, cur, new, tokens, 1)
+            O.decode_force_rows(logits, V1, 1, t, T, targets[r:], ntok[r:], lps[r:], tokens, score=score[r:])
+            cur, new = new, cur
+
+
+def caption_score_pairs(net, att_feats, fc_feats, tokens, lengths=None, rows=None, count=None):
+    """row r's own expression under row r's own mask (AttModel.forward + LanguageModelCriterion's gather for a batch of different
+    sentences): tokens int [rows][Tmax], ids 1 .. vocab_size, zero padded on the right (a host array, or device int64); lengths: the tokens
+    per row (default: its non-zeros), each 1 .. Tmax.  Row r is teacher-forced with the inputs [0, w_1 .. w_n] and the targets
+    [w_1 .. w_n, 0] -> on the device {'logprobs': f32 [rows][Tmax + 1], zero behind a row's n + 1; 'score': f32 [rows], their sum;
+    'ntok': int32 [rows] = n + 1}; zeros (ntok aside) in the rows at or beyond count[0].
+
+    Batched route: the token step runs the greedy way, its input the token l2s_decode_force_rows left for the row, so the launches per
+    token are caption_decode_rows' (att2in2 8, topdown 9) whatever `rows`, `count` and the lengths are; nothing comes back.  A row's
+    values do not depend on the other rows of its chunk as long as the chunk has two rows or more (a one-row chunk takes the
+    single-row linear kernels, another order of summation)."""
+    targets, ntok, T = _pairs_tokens(net, tokens, lengths, rows)
+    rows, att, fc = _start(net, 'caption_score_pairs', att_feats, fc_feats, targets.shape[0], count)
+    out = net.buf('rows.pairs_out', (rows * (T + 1),), f32, zero=True)
+    lps, score = out[:rows * T].view(rows, T), out[rows * T:]
+    if batched(net):
+        _pairs_batched(net, att, fc, rows, count, T, targets, ntok, lps, score)
+    else:
+        _pairs_loop(net, att, fc, rows, count, T, targets, ntok, lps, score)
+    return {'logprobs': lps, 'score': score, 'ntok': ntok}
 
 
 # ------------------------------------------------------------------ beam search on rows

@@ -1142,3 +1142,8 @@ class resnetv1(Network):
         """the teacher-forced log-likelihood of one expression (ints 1 .. vocab_size, length n) under `rows` masks -> device tensors
         {'logprobs' f32 [rows][n + 1], 'score' f32 [rows]}"""
         return caption_rows.caption_score_rows(self, att_feats, fc_feats, tokens, rows, count)
+
+    def caption_score_pairs(self, att_feats, fc_feats, tokens, lengths=None, rows=None, count=None):
+        """the teacher-forced log-likelihood of row r's own expression under row r's own mask: tokens int [rows][Tmax] (1 .. vocab_size,
+        zero padded) -> device tensors {'logprobs' f32 [rows][Tmax + 1], 'score' f32 [rows], 'ntok' int32 [rows] = n + 1}"""
+        return caption_rows.caption_score_pairs(self, att_feats, fc_feats, tokens, lengths, rows, count)

@@ -978,6 +978,22 @@ def decode_pick_rows(logits, V1, rows, t, T, finished, seq, logprobs, next_token
          ptr(logprobs), ptr(next_token), ptr(score), stream())
 
 
+def decode_force_rows(logits, V1, rows, t, T, targets, lengths, logprobs, next_token, count=None, row0=0, ld_logits=None, score=None):
+    """teacher forcing with a token row per row, step t of T: targets int64 [rows][T] (w_1 .. w_n, 0, padding), lengths int32 [rows]
+    (n + 1).  A row with t < lengths[r]: logprobs f32 [rows][T] column t = log_softmax(logits[r])[targets[r][t]] (decode_pick_rows' forced
+    arithmetic), added to score f32 [rows] (optional), next_token int64 [rows] = targets[r][t]; behind its length a row only gets
+    next_token = 0"""
+    _rows_count('decode_force_rows', rows, row0, count)
+    ld = V1 if ld_logits is None else ld_logits
+    if logits.dtype != torch.float32 or V1 < 1 or ld < V1 or logits.numel() < (rows - 1) * ld + V1 or not 0 <= t < T or \
+            min(targets.numel(), logprobs.numel()) < rows * T or min(lengths.numel(), next_token.numel()) < rows or \
+            targets.dtype != torch.int64 or lengths.dtype != torch.int32 or logprobs.dtype != torch.float32 or next_token.dtype != torch.int64 or \
+            (score is not None and (score.numel() < rows or score.dtype != torch.float32)):
+        raise ValueError('decode_force_rows: a buffer is smaller than rows = %d / V1 = %d / t = %d of T = %d ask, or has the wrong dtype' % (rows, V1, t, T))
+    call('l2s_decode_force_rows', ptr(logits), int(ld), int(V1), int(rows), int(row0), ptr(count), int(t), int(T), ptr(targets), ptr(lengths),
+         ptr(logprobs), ptr(next_token), ptr(score), stream())
+
+
 # ---- beam search on rows: `rows` detections with B beam rows each (group = B consecutive state rows per detection)
 def decode_beam_step_rows(logits, V1, B, t, T, rows, beam_seq, beam_seq_logprobs, beam_logprobs_sum, states, R, next_tokens, parents, done,
                           done_count, count=None, row0=0, ld_logits=None):

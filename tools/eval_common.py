@@ -46,6 +46,13 @@ def parse_args(argv=None):
     p.add_argument('--rerank_per_token', type=int, default=0, help='--rerank: divide expr_logprob by the expression\'s tokens + 1')
     p.add_argument('--dump_selection', default=None, help='with judging: write every sentence\'s choice per rule as one JSON list to this path '
                    '(rank suffix as above)')
+    p.add_argument('--caption_eval', type=int, default=0, help='with --device_eval 1 on cycle / cycle_response: evaluate the captioner too - every '
+                   'sentence\'s own expression (cut to seq_length tokens) scored teacher-forced under its ground-truth mask; prints loss, '
+                   'perplexity and loss_per_image, and --dump_predictions gains gt_expr_logprob / gt_expr_logprobs')
+    p.add_argument('--caption_eval_describe', type=int, default=0, help='--caption_eval 1: also the captioner\'s own sentence for every ground-truth '
+                   'mask (greedy, or the best of --beam_size beams) and the exact-match rate against the expression')
+    p.add_argument('--start_from', default=None, help='warm-start the captioner from <dataset_splitBy>/<start_from>/model-best.pth, as training '
+                   'does; --caption_eval prints its infos-best.pkl best_val_score beside the loss')
     # the expression encoder the snapshot was trained with (tools/opt.py; a snapshot of another encoder is an error that names the flag)
     # (default None: tools/opt.py's own defaults apply)
     p.add_argument('--rnn_type', default=None, help='lstm, gru or rnn'); p.add_argument('--rnn_num_layers', type=int, default=None)
@@ -98,6 +105,33 @@ def selection_options(args, variant):
     return judge, lambdas, bool(args.get('rerank_per_token'))
 
 
+def caption_eval_options(args, variant):
+    """the speaker's flags -> (caption_eval, describe, the beams of its descriptions).  ValueErrors name the flags involved"""
+    on, desc = bool(args.get('caption_eval')), bool(args.get('caption_eval_describe'))
+    if desc and not on:
+        raise ValueError('--caption_eval_describe 1 describes the ground-truth masks of the captioner\'s evaluation: it needs --caption_eval 1')
+    if on and not args.get('device_eval'):
+        raise ValueError('--caption_eval 1 runs inside the device evaluation: it needs --device_eval 1')
+    if on and variant not in ('cycle', 'cycle_response'):
+        raise ValueError('--caption_eval 1: --variant %s has no caption branch to evaluate (cycle and cycle_response have one)' % variant)
+    return on, desc, (args.get('beam_size', 1) if desc else 1)
+
+
+def print_caption_eval(t, infos=None):
+    """the speaker's line behind the usual summary; infos: the warm-start checkpoint's infos-best.pkl (context, not a check)"""
+    if not t or t.get('loss') is None:
+        print('Captioner: no sentence scored')
+        return
+    line = 'Captioner on the ground-truth masks (%d sents, %d tokens): loss %.4f, perplexity %.2f, loss_per_image %.4f' % (
+        t['num_sent'], t['num_tok'], t['loss'], t['perplexity'], t['loss_per_image'])
+    if t.get('exact_match') is not None:
+        line += ', exact match %.2f%%' % (t['exact_match'] * 100.0)
+    print(line)
+    if infos is not None and infos.get('best_val_score') is not None:
+        print('  -loss %.4f here; the checkpoint\'s own best_val_score %.4f (--start_from: its own features and its own validation split)' % (
+            -t['loss'], float(infos['best_val_score'])))
+
+
 def print_selection(totals):
     """one line per rule: det acc, seg acc at 0.5 and overall IoU of the detection that rule picks"""
     for name, t in totals.items():
@@ -123,7 +157,8 @@ def main(args, variant):
     for k in ('describe', 'expr_score'):
         if args.get(k) and not args.get('dump_detections'):
             raise ValueError('--%s 1 needs --dump_detections PATH: it adds fields to every detection (--%s, --dump_detections)' % (k, k))
-    if args.get('beam_size', 1) > 1 and not args.get('describe'):
+    cap_eval, cap_desc, cap_beams = caption_eval_options(args, variant)
+    if args.get('beam_size', 1) > 1 and not args.get('describe') and not cap_desc:
         raise ValueError('--beam_size %d without --describe 1: the beams are those of the captions of every detection (--beam_size, --describe)'
                          % args['beam_size'])
     if (args.get('describe') or args.get('expr_score')) and variant == 'vgg':
@@ -146,7 +181,7 @@ def main(args, variant):
     opt = parse_opt([])
     opt.update(vocab_size=loader.vocab_size, C4_feat_dim=1024, seq_length=loader.label_length,
                dataset_splitBy=args['dataset'] + '_' + args['splitBy'])
-    opt.update({k: args[k] for k in ('rnn_type', 'rnn_num_layers', 'bidirectional') if args.get(k) is not None})
+    opt.update({k: args[k] for k in ('rnn_type', 'rnn_num_layers', 'bidirectional', 'start_from') if args.get(k) is not None})
     if args['cfg_file'] and osp.exists(osp.join(ROOT, args['cfg_file'])):
         cfg_from_file(osp.join(ROOT, args['cfg_file']))
     if args['set_cfgs']:
@@ -193,9 +228,14 @@ def main(args, variant):
         from lang2seg_amd.model.eval_device import eval_split_device
         sel, sel_tot = ([], {}) if judge else (None, None)
         kw = dict(judge=True, rerank=lambdas, per_token=per_token, selection=sel, selection_totals=sel_tot) if judge else {}
+        cap_tot = {} if cap_eval else None
+        if cap_eval:
+            kw.update(caption_eval=True, caption_describe=cap_desc, caption_totals=cap_tot)
+            if cap_desc and not hasattr(loader, 'ix_to_word'):       # the synthetic stand-in has no words: w<id>, as tools/predict.py names them
+                eopt['ix_to_word'] = {str(i): 'w%d' % i for i in range(1, loader.vocab_size + 1)}
         res = eval_split_device(loader, net, None, split, eopt, rank=rank, world=world, predictions=preds, detections=dets,
                                 describe=bool(args.get('describe')), expr_score=bool(args.get('expr_score')),
-                                beam_size=args.get('beam_size', 1) if args.get('describe') else 1, **kw)
+                                beam_size=args.get('beam_size', 1) if (args.get('describe') or cap_desc) else 1, **kw)
         dump_predictions(args, preds, rank, world)
         dump_predictions(args, dets, rank, world, 'dump_detections', 'detections')
         if args.get('dump_selection'):
@@ -211,6 +251,13 @@ def main(args, variant):
     print(results_str)
     if args['device_eval'] and judge:
         print_selection(sel_tot)
+    if args['device_eval'] and cap_eval:
+        infos = None
+        if opt.get('start_from') is not None:
+            from lang2seg_amd.utils.caption_ckpt import read_infos, start_dir
+            f = osp.join(start_dir(opt, opt.get('checkpoint_root', '.')), 'infos-best.pkl')
+            infos = read_infos(f) if osp.isfile(f) else None
+        print_caption_eval(cap_tot, infos)
     # tools/eval_spatial.py:95-98,121-124: the two running result logs
     res_dir = args.get('results_dir') or osp.join(ROOT, 'experiments')
     os.makedirs(res_dir, exist_ok=True)
