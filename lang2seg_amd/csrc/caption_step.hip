@@ -665,7 +665,7 @@ extern "C" int l2s_cap_a2c_gates_fwd(const float* att_res, const float* w_a2c, c
 }
 extern "C" int l2s_cap_attention_bwd_step(const float* datt_res, const float* att, const float* tanh_ws, const float* weight, const float* aw, int L,
                                           int D, float* ddot, float* datt_h, hipStream_t s) {
-  if (L > 256 || (D & 3)) return L2S_EINVAL;
+  if (L > 256 || (D & 3) || ((uintptr_t)datt_res & 15) || ((uintptr_t)att & 15)) return L2S_EINVAL;
   L2S_LAUNCH(cap_att_bwd_step_kernel, dim3(cdiv(D, 16)), dim3(1024), 0, s, datt_res, att, tanh_ws, weight, aw, L, D, ddot, datt_h);
   return l2s_check_launch();
 }

@@ -199,7 +199,7 @@ extern "C" int l2s_lstm_cell_bwd(const float* dh, const float* dc_in, const floa
 }
 #ifndef L2S_LSTM_STEP_FWD_EXTERNAL   // tools/lstm_pk_probe.sh links tools/lstm_pk_probe.hip's entry (and kernel variants) in place of this one
 extern "C" int l2s_lstm_step_fwd(const l2s_lstm_fwd_dir* dirs, int ndir, int Hh, hipStream_t s) {
-  if (!dirs || ndir < 1 || ndir > 2 || (Hh & 3)) return L2S_EINVAL;
+  if (!dirs || ndir < 1 || ndir > 2 || Hh < 4 || (Hh & 3)) return L2S_EINVAL;
   LstmDir a[2];
   for (int i = 0; i < 2; ++i) { const l2s_lstm_fwd_dir& q = dirs[i < ndir ? i : 0]; a[i] = LstmDir{q.w_hh, q.b_hh, q.gates_in, q.h_prev, q.c_prev, q.c, q.h, q.act, q.gates_out}; }
   L2S_LAUNCH(lstm_step_fwd_kernel, dim3(cdiv(Hh, 4), ndir), dim3(256), 0, s, a[0], a[1], Hh);
@@ -207,7 +207,7 @@ extern "C" int l2s_lstm_step_fwd(const l2s_lstm_fwd_dir* dirs, int ndir, int Hh,
 }
 #endif
 extern "C" int l2s_lstm_step_bwd(const l2s_lstm_bwd_dir* dirs, int ndir, int Hh, hipStream_t s) {
-  if (!dirs || ndir < 1 || ndir > 2 || (Hh & 3)) return L2S_EINVAL;
+  if (!dirs || ndir < 1 || ndir > 2 || Hh < 4 || (Hh & 3)) return L2S_EINVAL;
   LstmBDir a[2];
   for (int i = 0; i < 2; ++i) { const l2s_lstm_bwd_dir& q = dirs[i < ndir ? i : 0]; a[i] = LstmBDir{q.w_hh_T, q.dgates_next, q.dh_ext, q.dc_in, q.act, q.c_prev, q.c, q.dgates, q.dc_prev}; }
   L2S_LAUNCH(lstm_step_bwd_kernel, dim3(cdiv(Hh, 4), ndir), dim3(256), 0, s, a[0], a[1], Hh);
